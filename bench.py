@@ -15,8 +15,13 @@ Reproduces the reference's published scenario (10 M base rows
 value = merged output rows/sec aggregated over all N GPUs (whole job).
 Weak scaling: per-GPU table shard is fixed as N grows.
 
-Run:  python bench.py --gpus N --steps K --warmup W
+Run:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (driver launches via torch.distributed.run for N>1; RANK/WORLD_SIZE env)
+
+A plain run sets up, warms up, times the K steps and prints one JSON
+result line. --dump-outputs DIR additionally writes the merged columns of
+the last timed step as DIR/<column>.npy; --full enables the secondary
+measurements that take a scan of their own.
 """
 
 import argparse
@@ -53,7 +58,48 @@ def build_args():
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--workdir", type=str, default=None)
     p.add_argument("--keep", action="store_true")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the merged columns of the last timed step to "
+                        "DIR/<column>.npy (a fixed seeded row sample)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that take a "
+                        "scan of their own (the cProfile step when "
+                        "LAKESOUL_PROFILE=1); a plain run only sets up, "
+                        "warms up and times the headline steps")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+DUMP_MAX_ROWS = 1_000_000  # x 44 B/row (5 columns + row position) = 44 MB
+
+
+def dump_outputs(out_dir, batches, rank, world):
+    """Write what the last timed scan returned: every column of the merged
+    batches, concatenated in the order the scan yielded them. Outputs
+    larger than DUMP_MAX_ROWS are reduced to a fixed seeded sample of row
+    positions (sorted, so the scan order is kept), identical from run to
+    run. Integer columns are stored as float64 (exact below 2**53), f as
+    float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = sum(b.num_rows for b in batches)
+    if n > DUMP_MAX_ROWS:
+        pick = np.sort(np.random.default_rng(20240917).choice(
+            n, DUMP_MAX_ROWS, replace=False))
+    else:
+        pick = np.arange(n)
+    suffix = "" if world == 1 else f".rank{rank}"
+    names = list(batches[0].columns) if batches else []
+    for name in names:
+        col = np.concatenate([b.column(name).to_numpy() for b in batches])
+        out_dt = np.float32 if col.dtype == np.float32 else np.float64
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                col[pick].astype(out_dt))
+    np.save(os.path.join(out_dir, f"num_rows{suffix}.npy"),
+            np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, f"sample_rows{suffix}.npy"),
+            pick.astype(np.float64))
 
 
 def main():
@@ -187,12 +233,13 @@ def main():
         dist.barrier()
 
     # ---------------- timed: MOR scan steps ---------------- #
-    def one_scan() -> int:
+    def one_scan(keep=None) -> int:
         """Timed step: MOR scan of this rank's buckets; for N>1 each merged
         batch is re-sharded across ranks by spark-murmur3 of the PK — the
         real rebalance_by_pk exchange (one packed RCCL all-to-all over
         xGMI per batch), enqueued async so it overlaps the next unit's
-        decode."""
+        decode. ``keep`` (a list) retains the merged batches for
+        --dump-outputs."""
         from lakesoul_amd.parallel.shard import rebalance_by_pk_async
 
         scan = table.scan(device=device).shard(rank, world)
@@ -200,6 +247,8 @@ def main():
         pending = None
         for batch in scan.iter_batches():
             total += batch.num_rows
+            if keep is not None:
+                keep.append(batch)
             if dist is not None:
                 if pending is not None:
                     pending.wait()
@@ -215,7 +264,7 @@ def main():
 
     if _tm.ENABLED:
         _tm.reset()  # report warm steps only
-    if os.environ.get("LAKESOUL_PROFILE") == "1" and rank == 0:
+    if args.full and os.environ.get("LAKESOUL_PROFILE") == "1" and rank == 0:
         import cProfile, pstats, io as _io
 
         pr = cProfile.Profile()
@@ -227,10 +276,17 @@ def main():
         print(s.getvalue(), file=sys.stderr, flush=True)
     t_start = time.time()
     rows_per_step = 0
+    last_batches = [] if args.dump_outputs else None
     for s in range(args.steps):
-        rows_per_step = one_scan()
+        # only the last timed step's batches are retained for the dump
+        rows_per_step = one_scan(
+            last_batches if s == args.steps - 1 else None)
     barrier()
     elapsed = time.time() - t_start
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_batches, rank, world)
+        del last_batches
 
     # max over ranks
     if dist is not None:

@@ -458,7 +458,11 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
       int64_t es = da[u][3];
       if (da[u][2]) {  // dict
         auto rr = runs2.narrow(0, da[u][11], da[u][12]);
-        auto payload = vals.narrow(0, da[u][6], da[u][7]);
+        // run bit offsets are relative to the whole values buffer (they
+        // already include this chunk's val_off, see read_unit.h)
+        TORCH_CHECK(da[u][6] + da[u][7] <= vals.numel(),
+                    "scan_unit_uselast: dict payload out of range");
+        auto payload = vals;
         auto idx = torch::empty({da[u][13]}, torch::TensorOptions().dtype(torch::kInt32).device(device));
         launch_rle_expand(payload.data_ptr<uint8_t>(), rr.data_ptr<int64_t>(),
                           rr.size(0), idx.data_ptr<int32_t>(), da[u][13], stream);

@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from .. import constants
 from ..ops import cpp, hip
 from ..utils import timing
 from .batch import Batch, Column, torch_dtype_for
@@ -391,8 +392,9 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None,
             esize = _ESIZE[tdt]
             if cd["is_dict"]:
                 runs = runs_buf.narrow(0, cd["run_off"], cd["run_cnt"])
-                payload = vals.narrow(0, cd["val_off"], cd["val_len"])
-                idx = hip().rle_expand(payload, runs, cd["dense_n"])
+                # run bit offsets are relative to the whole values buffer
+                # (they already include this chunk's val_off)
+                idx = hip().rle_expand(vals, runs, cd["dense_n"])
                 dict_vals = dicts_buf.narrow(0, cd["dict_off"], cd["dict_len"])
                 if vmask is not None:
                     pos = torch.cumsum(vmask.to(torch.int64), 0) - 1
@@ -467,19 +469,30 @@ def _decode_fixed_chunk_gpu(d: dict, dtype: str, device) -> Column:
 
 
 def _range_col_gpu(scan, f, unit, n, device) -> Column:
-    val = None
+    # same semantics as the CPU path (LakeSoulScan._range_value_column):
+    # values are sentinel-decoded (NULL/''/','/'=' round trip); the NULL
+    # sentinel materializes as an all-null column
+    val, found = None, False
     for kv in unit.partition_desc.split(","):
         if "=" in kv and kv.split("=", 1)[0] == f.name:
-            val = kv.split("=", 1)[1]
+            val = constants.decode_partition_value(kv.split("=", 1)[1])
+            found = True
+    is_null = found and val is None
+    validity = (torch.zeros(n, dtype=torch.uint8, device=device)
+                if is_null else None)
     if f.is_fixed_width:
         tdt = torch_dtype_for(f.dtype)
-        x = float(val) if f.dtype.startswith("float") else int(val) if val is not None else 0
-        return Column(f.dtype, data=torch.full((n,), x, dtype=tdt, device=device))
+        if not found or is_null:
+            x = 0
+        else:
+            x = float(val) if f.dtype.startswith("float") else int(val)
+        return Column(f.dtype, data=torch.full((n,), x, dtype=tdt, device=device),
+                      validity=validity)
     enc = (val or "").encode()
     offs = torch.arange(n + 1, dtype=torch.int64, device=device) * len(enc)
     bys = (
         torch.frombuffer(bytearray(enc * n), dtype=torch.uint8).to(device)
-        if n
+        if n and enc
         else torch.empty(0, dtype=torch.uint8, device=device)
     )
-    return Column(f.dtype, offsets=offs, bytes_=bys)
+    return Column(f.dtype, offsets=offs, bytes_=bys, validity=validity)

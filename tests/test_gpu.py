@@ -768,3 +768,89 @@ def test_gpu_oversized_string_pk_chunked(dev, tmp_path, monkeypatch):
     import pandas as pd
 
     pd.testing.assert_frame_equal(full, df)
+
+
+@pytest.mark.parametrize("pks", [["id"], ["id", "id2"]],
+                         ids=["fast_path", "generic_path"])
+def test_gpu_foreign_dict_delta_mor(dev, tmp_path, pks):
+    """A dictionary-encoded (pyarrow, snappy) delta file merged with our
+    PLAIN zstd base file: the dict index payload sits at a non-zero offset
+    of the unit's values buffer (it follows the base file's columns) in
+    both the native one-call unit path and the generic per-column path."""
+    import os
+
+    import pandas as pd
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    from lakesoul_amd.io.schema import Field, Schema
+    from lakesoul_amd.meta.entities import (CommitOp, DataCommitInfo,
+                                            DataFileOp, FileOp)
+
+    catalog = _mk_catalog(tmp_path)
+    t = catalog.create_table(
+        "gforeign",
+        Schema([Field("id", "int64", False), Field("id2", "int64", False),
+                Field("v", "float64"), Field("s", "string")]),
+        primary_keys=pks, hash_bucket_num=1,
+    )
+    n, m = 5000, 1000
+    t.upsert({"id": np.arange(n, dtype=np.int64),
+              "id2": np.arange(n, dtype=np.int64) % 7,
+              "v": np.zeros(n), "s": ["ours"] * n}, device="cpu")
+    foreign = str(tmp_path / "part-foreign0000000_0000.parquet")
+    pq.write_table(pa.table({
+        "id": pa.array(np.arange(m, dtype=np.int64)),
+        "id2": pa.array(np.arange(m, dtype=np.int64) % 7),
+        "v": pa.array(np.arange(m, dtype=np.float64) % 13 + 0.5),
+        "s": pa.array(["theirs"] * m),
+    }), foreign, use_dictionary=True, compression="snappy")
+    t.client.commit_data_commit_info(DataCommitInfo(
+        table_id=t.table_id, partition_desc="-5",
+        file_ops=[DataFileOp(foreign, FileOp.add, os.path.getsize(foreign))],
+        commit_op=CommitOp.MergeCommit,
+    ))
+    cpu = t.scan(device="cpu").to_arrow().to_pandas()
+    gpu = t.scan(device="cuda").to_arrow().to_pandas()
+    cpu = cpu.sort_values("id").reset_index(drop=True)
+    gpu = gpu.sort_values("id").reset_index(drop=True)
+    assert len(gpu) == n
+    pd.testing.assert_frame_equal(cpu, gpu)
+    assert (gpu["s"][:m] == "theirs").all() and (gpu["s"][m:] == "ours").all()
+    np.testing.assert_array_equal(
+        gpu["v"][:m].to_numpy(), np.arange(m, dtype=np.float64) % 13 + 0.5)
+
+
+def test_gpu_range_partition_special_values(dev, tmp_path):
+    """Range-partition values with ',', '=', '' and NULL (string and
+    numeric) round-trip through the partition_desc sentinels on the GPU
+    scan exactly as on the CPU scan."""
+    import pandas as pd
+
+    from lakesoul_amd.io.schema import Field, Schema
+
+    catalog = _mk_catalog(tmp_path)
+    t = catalog.create_table(
+        "grange_special",
+        Schema([Field("city", "string"), Field("yr", "int32"),
+                Field("id", "int64", False), Field("v", "float64")]),
+        primary_keys=["id"], range_partitions=["city", "yr"],
+        hash_bucket_num=2,
+    )
+    cities = ["a,b", "x=y", "", None, "plain"]
+    years = [2024, None, 2025, 2026, None]
+    for v in (0.0, 1.0):  # two commits per partition: units with a merge
+        t.upsert(pd.DataFrame({
+            "city": cities, "yr": pd.array(years, dtype="Int32"),
+            "id": np.arange(5, dtype=np.int64), "v": np.full(5, v),
+        }), device="cpu")
+    cpu = t.scan(device="cpu").to_arrow().to_pandas()
+    gpu = t.scan(device="cuda").to_arrow().to_pandas()
+    cpu = cpu.sort_values("id").reset_index(drop=True)
+    gpu = gpu.sort_values("id").reset_index(drop=True)
+    pd.testing.assert_frame_equal(cpu, gpu)
+    got = gpu["city"].tolist()
+    assert got[0] == "a,b" and got[1] == "x=y" and got[2] == ""
+    assert pd.isna(got[3]) and got[4] == "plain"
+    assert gpu["yr"].isna().tolist() == [False, True, False, False, True]
+    assert gpu["v"].tolist() == [1.0] * 5
