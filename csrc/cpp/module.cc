@@ -14,6 +14,7 @@
 #include "murmur3.h"
 #include "parquet_file.h"
 #include "read_unit.h"
+#include "unit_desc.h"
 #include "zstd_dec.h"
 
 namespace py = pybind11;
@@ -579,46 +580,6 @@ static py::list read_chunks_raw_batch(int64_t h,
   return result;
 }
 
-// prep dictionary-index RLE runs for the GPU expansion kernel:
-// idx_pages int64 [p,5] = {row_off, n_nonnull, payload_off, payload_len, bw}
-// returns (payload padded +8 bytes, runs int64 [m,5] =
-//          {dense_out_off, n, is_literal, value_or_abs_bitoff, bit_width},
-//          total_dense_n)
-static py::tuple prep_rle_runs(torch::Tensor values, torch::Tensor idx_pages) {
-  auto v = values.contiguous();
-  auto pages = idx_pages.contiguous();
-  const uint8_t* base = v.data_ptr<uint8_t>();
-  auto pa = pages.accessor<int64_t, 2>();
-  std::vector<RleRun> all;
-  int64_t dense_off = 0;
-  std::vector<int64_t> bws;
-  for (int64_t p = 0; p < pages.size(0); p++) {
-    int64_t n = pa[p][1], off = pa[p][2], len = pa[p][3];
-    int bw = (int)pa[p][4];
-    std::vector<RleRun> runs;
-    parse_rle_runs(base + off, (size_t)len, bw, n, off * 8, runs);
-    for (auto& r : runs) {
-      r.out_off += dense_off;
-      all.push_back(r);
-      bws.push_back(bw);
-    }
-    dense_off += n;
-  }
-  auto runs_t = torch::empty({(int64_t)all.size(), 6}, torch::kInt64);
-  auto ra = runs_t.accessor<int64_t, 2>();
-  for (size_t i = 0; i < all.size(); i++) {
-    ra[i][0] = all[i].out_off;
-    ra[i][1] = all[i].n;
-    ra[i][2] = all[i].is_literal;
-    ra[i][3] = all[i].is_literal ? all[i].bit_off : (int64_t)all[i].value;
-    ra[i][4] = bws[i];
-    ra[i][5] = 0;
-  }
-  auto padded = torch::zeros({v.numel() + 8}, torch::kUInt8);
-  std::memcpy(padded.data_ptr(), base, v.numel());
-  return py::make_tuple(padded, runs_t, dense_off);
-}
-
 // read all files of a scan unit in one call; big contiguous buffers for
 // single-H2D GPU decode (see read_unit.h). ``pin`` requests pinned host
 // memory for the big buffers (GPU boxes).
@@ -688,58 +649,32 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   py::list frows;
   for (auto r : ud.file_rows) frows.append(r);
   d["file_rows"] = frows;
-  // descriptor tensor for the C++ scan driver: [nuc, 17]
-  {
-    auto dt = torch::empty({(int64_t)ud.cols.size(), 17}, torch::kInt64);
-    auto da = dt.accessor<int64_t, 2>();
-    for (size_t i = 0; i < ud.cols.size(); i++) {
-      const UnitColumn& c = ud.cols[i];
-      int es = c.present && !c.is_string ? physical_elem_size(c.physical) : 0;
-      da[i][0] = c.present;
-      da[i][1] = c.is_string;
-      da[i][2] = c.is_dict;
-      da[i][3] = es;
-      da[i][4] = c.num_values;
-      da[i][5] = c.null_count;
-      da[i][6] = c.val_off;
-      da[i][7] = c.val_len;
-      da[i][8] = c.validity_off;
-      da[i][9] = c.dict_off;
-      da[i][10] = c.dict_len;
-      da[i][11] = c.run_off;
-      da[i][12] = c.run_cnt;
-      da[i][13] = c.dense_n;
-      da[i][14] = c.soff_off;
-      da[i][15] = c.sbytes_off;
-      da[i][16] = c.sbytes_len;
-    }
-    d["desc"] = dt;
+  // descriptor tensor for the GPU decoder (layout: unit_desc.h)
+  auto dt = torch::empty({(int64_t)ud.cols.size(), UD_NFIELDS}, torch::kInt64);
+  auto da = dt.accessor<int64_t, 2>();
+  for (size_t i = 0; i < ud.cols.size(); i++) {
+    const UnitColumn& c = ud.cols[i];
+    da[i][UD_PRESENT] = c.present;
+    da[i][UD_IS_STRING] = c.is_string;
+    da[i][UD_IS_LIST] = c.is_list;
+    da[i][UD_IS_DICT] = c.is_dict;
+    da[i][UD_ESIZE] =
+        c.present && !c.is_string ? physical_elem_size(c.physical) : 0;
+    da[i][UD_NUM_VALUES] = c.num_values;
+    da[i][UD_NULL_COUNT] = c.null_count;
+    da[i][UD_VAL_OFF] = c.val_off;
+    da[i][UD_VAL_LEN] = c.val_len;
+    da[i][UD_VALIDITY_OFF] = c.validity_off;
+    da[i][UD_DICT_OFF] = c.dict_off;
+    da[i][UD_DICT_LEN] = c.dict_len;
+    da[i][UD_RUN_OFF] = c.run_off;
+    da[i][UD_RUN_CNT] = c.run_cnt;
+    da[i][UD_DENSE_N] = c.dense_n;
+    da[i][UD_SOFF_OFF] = c.soff_off;
+    da[i][UD_SBYTES_OFF] = c.sbytes_off;
+    da[i][UD_SBYTES_LEN] = c.sbytes_len;
   }
-  py::list cols;
-  for (auto& c : ud.cols) {
-    py::dict cd;
-    cd["file_idx"] = c.file_idx;
-    cd["name"] = c.name;
-    cd["present"] = c.present;
-    cd["is_string"] = c.is_string;
-    cd["is_list"] = c.is_list;
-    cd["is_dict"] = c.is_dict;
-    cd["num_values"] = c.num_values;
-    cd["null_count"] = c.null_count;
-    cd["val_off"] = c.val_off;
-    cd["val_len"] = c.val_len;
-    cd["validity_off"] = c.validity_off;
-    cd["dict_off"] = c.dict_off;
-    cd["dict_len"] = c.dict_len;
-    cd["run_off"] = c.run_off;
-    cd["run_cnt"] = c.run_cnt;
-    cd["dense_n"] = c.dense_n;
-    cd["soff_off"] = c.soff_off;
-    cd["sbytes_off"] = c.sbytes_off;
-    cd["sbytes_len"] = c.sbytes_len;
-    cols.append(cd);
-  }
-  d["cols"] = cols;
+  d["desc"] = dt;
   // free the staging structures (dozens of MB of chunk vectors) off the
   // critical path — destructor cost was visible in the fetch time
   std::thread([p = st.release()]() { delete p; }).detach();
@@ -939,11 +874,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("read_chunk_raw", &read_chunk_raw);
   m.def("read_chunk_cpu", &read_chunk_cpu);
   m.def("read_chunks_cpu_batch", &read_chunks_cpu_batch);
-  m.def("prep_rle_runs", &prep_rle_runs);
   m.def("read_unit_raw", &read_unit_raw_py, py::arg("paths"), py::arg("names"),
         py::arg("nthreads") = 0, py::arg("pin") = true,
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
         py::arg("gpu_zstd_frac") = 1.0);
+  // the one descriptor column python looks at (fast-path eligibility)
+  m.attr("UD_PRESENT") = (int)UD_PRESENT;
   m.def("read_chunks_raw_batch", &read_chunks_raw_batch);
   m.def("zstd_compress_ref", [](py::bytes src, int64_t level) {
     std::string b = src;

@@ -1,0 +1,26 @@
+// Column layout of the scan-unit descriptor tensor (int64 [nfiles*ncols,
+// UD_NFIELDS], row = file * ncols + col): written by _cpp.read_unit_raw,
+// read by _hip.decode_unit / _hip.scan_unit_uselast.
+#pragma once
+
+enum UnitDescField {
+  UD_PRESENT = 0,
+  UD_IS_STRING,
+  UD_IS_LIST,  // element offsets in soffs, element payload at sbytes
+  UD_IS_DICT,
+  UD_ESIZE,  // physical element size in bytes (0 for strings)
+  UD_NUM_VALUES,
+  UD_NULL_COUNT,
+  UD_VAL_OFF,
+  UD_VAL_LEN,
+  UD_VALIDITY_OFF,  // -1: no validity region
+  UD_DICT_OFF,
+  UD_DICT_LEN,
+  UD_RUN_OFF,
+  UD_RUN_CNT,
+  UD_DENSE_N,
+  UD_SOFF_OFF,
+  UD_SBYTES_OFF,
+  UD_SBYTES_LEN,
+  UD_NFIELDS
+};

@@ -5,6 +5,8 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include "../cpp/unit_desc.h"
+
 namespace py = pybind11;
 
 namespace lakesoul {
@@ -143,6 +145,36 @@ static torch::Tensor rle_expand(torch::Tensor payload, torch::Tensor runs, int64
   return out;
 }
 
+// element-size dispatch, written once for the bindings and decode_unit
+static void dict_gather_scatter_es(int64_t es, const void* dict_vals,
+                                   const int32_t* idx, const uint8_t* vmask,
+                                   const int64_t* pos, void* out, int64_t n,
+                                   hipStream_t stream) {
+  if (es == 4)
+    launch_dict_gather_scatter<uint32_t>((const uint32_t*)dict_vals, idx, vmask, pos, (uint32_t*)out, n, stream);
+  else if (es == 8)
+    launch_dict_gather_scatter<uint64_t>((const uint64_t*)dict_vals, idx, vmask, pos, (uint64_t*)out, n, stream);
+  else if (es == 1)
+    launch_dict_gather_scatter<uint8_t>((const uint8_t*)dict_vals, idx, vmask, pos, (uint8_t*)out, n, stream);
+  else
+    TORCH_CHECK(false, "dict_gather_scatter: unsupported elem size ", es);
+}
+
+static void scatter_valid_es(int64_t es, const void* dense, const uint8_t* vmask,
+                             const int64_t* pos, void* out, int64_t n,
+                             hipStream_t stream) {
+  if (es == 1)
+    launch_scatter_valid<uint8_t>((const uint8_t*)dense, vmask, pos, (uint8_t*)out, n, stream);
+  else if (es == 2)
+    launch_scatter_valid<uint16_t>((const uint16_t*)dense, vmask, pos, (uint16_t*)out, n, stream);
+  else if (es == 4)
+    launch_scatter_valid<uint32_t>((const uint32_t*)dense, vmask, pos, (uint32_t*)out, n, stream);
+  else if (es == 8)
+    launch_scatter_valid<uint64_t>((const uint64_t*)dense, vmask, pos, (uint64_t*)out, n, stream);
+  else
+    TORCH_CHECK(false, "scatter_valid: unsupported elem size ", es);
+}
+
 static torch::Tensor dict_gather_scatter(torch::Tensor dict_vals, torch::Tensor idx,
                                          torch::Tensor validity, torch::Tensor positions,
                                          int64_t elem_size, int64_t n) {
@@ -151,23 +183,10 @@ static torch::Tensor dict_gather_scatter(torch::Tensor dict_vals, torch::Tensor 
   CHECK_GPU(dict_vals);
   CHECK_GPU(idx);
   auto out = torch::empty({n * elem_size}, dict_vals.options().dtype(torch::kUInt8));
-  const uint8_t* vmask = opt_u8(validity);
-  const int64_t* pos = validity.numel() ? positions.data_ptr<int64_t>() : nullptr;
-  if (elem_size == 4) {
-    launch_dict_gather_scatter<uint32_t>(
-        (const uint32_t*)dict_vals.data_ptr(), idx.data_ptr<int32_t>(), vmask,
-        pos, (uint32_t*)out.data_ptr(), n, cur_stream());
-  } else if (elem_size == 8) {
-    launch_dict_gather_scatter<uint64_t>(
-        (const uint64_t*)dict_vals.data_ptr(), idx.data_ptr<int32_t>(), vmask,
-        pos, (uint64_t*)out.data_ptr(), n, cur_stream());
-  } else if (elem_size == 1) {
-    launch_dict_gather_scatter<uint8_t>(
-        dict_vals.data_ptr<uint8_t>(), idx.data_ptr<int32_t>(), vmask, pos,
-        out.data_ptr<uint8_t>(), n, cur_stream());
-  } else {
-    TORCH_CHECK(false, "unsupported elem size");
-  }
+  dict_gather_scatter_es(
+      elem_size, dict_vals.data_ptr(), idx.data_ptr<int32_t>(), opt_u8(validity),
+      validity.numel() ? positions.data_ptr<int64_t>() : nullptr, out.data_ptr(),
+      n, cur_stream());
   return out;
 }
 
@@ -178,14 +197,8 @@ static torch::Tensor scatter_valid(torch::Tensor dense, torch::Tensor validity,
   CHECK_GPU_NONEMPTY(positions);
   CHECK_GPU(dense);
   auto out = torch::zeros({n * elem_size}, dense.options().dtype(torch::kUInt8));
-  if (elem_size == 1)
-    launch_scatter_valid<uint8_t>(dense.data_ptr<uint8_t>(), validity.data_ptr<uint8_t>(), positions.data_ptr<int64_t>(), out.data_ptr<uint8_t>(), n, cur_stream());
-  else if (elem_size == 2)
-    launch_scatter_valid<uint16_t>((const uint16_t*)dense.data_ptr(), validity.data_ptr<uint8_t>(), positions.data_ptr<int64_t>(), (uint16_t*)out.data_ptr(), n, cur_stream());
-  else if (elem_size == 4)
-    launch_scatter_valid<uint32_t>((const uint32_t*)dense.data_ptr(), validity.data_ptr<uint8_t>(), positions.data_ptr<int64_t>(), (uint32_t*)out.data_ptr(), n, cur_stream());
-  else
-    launch_scatter_valid<uint64_t>((const uint64_t*)dense.data_ptr(), validity.data_ptr<uint8_t>(), positions.data_ptr<int64_t>(), (uint64_t*)out.data_ptr(), n, cur_stream());
+  scatter_valid_es(elem_size, dense.data_ptr(), validity.data_ptr<uint8_t>(),
+                   positions.data_ptr<int64_t>(), out.data_ptr(), n, cur_stream());
   return out;
 }
 
@@ -397,119 +410,152 @@ static std::vector<torch::Tensor> snappy_decompress(torch::Tensor src,
 }
 
 // ---------------------------------------------------------------------- //
-// C++ scan-unit driver (simple path): decode + UseLast merge + gather for
-// one unit entirely from C++ — the python per-unit op storm (GIL-bound)
-// was the scan's critical path. Covers: integer single-PK (int64/int32),
-// every-column UseLast, no CDC. Python falls back otherwise.
-//
-// desc: int64 [nuc,17] from _cpp.read_unit_raw (see module.cc):
-// {present,is_string,is_dict,esize,num_values,null_count,val_off,val_len,
-//  validity_off,dict_off,dict_len,run_off,run_cnt,dense_n,soff_off,
-//  sbytes_off,sbytes_len}
-// Returns: [n_out scalar?] -> list: for each read col:
-//   fixed: [data_u8_gathered, validity_or_empty]
-//   string: [offsets_i64, bytes_u8, validity_or_empty]
-// plus the merged row count implicit in tensor sizes.
-static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf,
-                                  torch::Tensor dicts, torch::Tensor runs,
-                                  torch::Tensor soffs, torch::Tensor desc,
-                                  int64_t nfiles, int64_t ncols, int64_t pk_ci,
-                                  int64_t pk_es) {
+// Scan-unit decode: every (file, column) chunk of one unit into dense
+// device columns. desc: int64 [nfiles*ncols, UD_NFIELDS] from
+// _cpp.read_unit_raw (layout: unit_desc.h). The one chunk decoder under
+// both read_unit_gpu paths: scan_unit_uselast below, and the python-driven
+// merge through the decode_unit binding.
+struct UnitCol {
+  bool present = false, is_string = false, is_list = false;
+  torch::Tensor data;             // fixed width: es bytes per row
+  torch::Tensor offsets, bytes;   // string: byte offsets; list: ELEMENT offsets
+  torch::Tensor validity;         // undefined = all valid
+};
+
+static std::vector<UnitCol> decode_unit_cols(
+    const torch::Tensor& vals, const torch::Tensor& validity_buf,
+    const torch::Tensor& dicts, const torch::Tensor& runs,
+    const torch::Tensor& soffs, const torch::Tensor& desc, int64_t nfiles,
+    int64_t ncols) {
   CHECK_GPU_NONEMPTY(validity_buf);
   CHECK_GPU_NONEMPTY(dicts);
   CHECK_GPU_NONEMPTY(runs);
   CHECK_GPU_NONEMPTY(soffs);
   CHECK_GPU(vals);
+  TORCH_CHECK(desc.is_cpu() && desc.scalar_type() == torch::kInt64 &&
+                  desc.dim() == 2 && desc.size(0) == nfiles * ncols &&
+                  desc.size(1) == UD_NFIELDS,
+              "decode_unit: desc must be a CPU int64 [nfiles*ncols, UD_NFIELDS] tensor");
+  auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(vals.device());
+  auto da = desc.accessor<int64_t, 2>();
+  auto stream = cur_stream();
+  torch::Tensor runs2 = runs.numel() ? runs.view({-1, 6}) : runs;
+
+  std::vector<UnitCol> cols((size_t)(nfiles * ncols));
+  for (int64_t u = 0; u < nfiles * ncols; u++) {
+    UnitCol& out = cols[(size_t)u];
+    const auto d = da[u];
+    if (!d[UD_PRESENT]) continue;
+    out.present = true;
+    int64_t nv = d[UD_NUM_VALUES];
+    bool has_null = d[UD_VALIDITY_OFF] >= 0 && d[UD_NULL_COUNT] > 0;
+    if (has_null) out.validity = validity_buf.narrow(0, d[UD_VALIDITY_OFF], nv);
+    const torch::Tensor& vmask = out.validity;
+    if (d[UD_IS_STRING] || d[UD_IS_LIST]) {
+      out.is_string = d[UD_IS_STRING];
+      out.is_list = d[UD_IS_LIST];
+      out.offsets = soffs.narrow(0, d[UD_SOFF_OFF], nv + 1);
+      out.bytes = vals.narrow(0, d[UD_SBYTES_OFF], d[UD_SBYTES_LEN]);
+      continue;
+    }
+    int64_t es = d[UD_ESIZE];
+    if (d[UD_IS_DICT]) {
+      auto rr = runs2.narrow(0, d[UD_RUN_OFF], d[UD_RUN_CNT]);
+      // run bit offsets are relative to the whole values buffer (they
+      // already include this chunk's val_off, see read_unit.h)
+      TORCH_CHECK(d[UD_VAL_OFF] + d[UD_VAL_LEN] <= vals.numel(),
+                  "decode_unit: dict payload out of range");
+      auto idx = torch::empty({d[UD_DENSE_N]}, u8.dtype(torch::kInt32));
+      launch_rle_expand(vals.data_ptr<uint8_t>(), rr.data_ptr<int64_t>(),
+                        rr.size(0), idx.data_ptr<int32_t>(), d[UD_DENSE_N], stream);
+      auto dv = dicts.narrow(0, d[UD_DICT_OFF], d[UD_DICT_LEN]);
+      out.data = torch::empty({nv * es}, u8);
+      torch::Tensor pos;
+      if (has_null) pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
+      dict_gather_scatter_es(es, dv.data_ptr(), idx.data_ptr<int32_t>(),
+                             has_null ? vmask.data_ptr<uint8_t>() : nullptr,
+                             has_null ? pos.data_ptr<int64_t>() : nullptr,
+                             out.data.data_ptr(), nv, stream);
+    } else {
+      auto dense = vals.narrow(0, d[UD_VAL_OFF], d[UD_VAL_LEN]);
+      if (has_null) {
+        auto pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
+        out.data = torch::zeros({nv * es}, u8);
+        scatter_valid_es(es, dense.data_ptr(), vmask.data_ptr<uint8_t>(),
+                         pos.data_ptr<int64_t>(), out.data.data_ptr(), nv, stream);
+      } else {
+        out.data = dense;
+      }
+    }
+  }
+  return cols;
+}
+
+static py::object tensor_or_none(const torch::Tensor& t) {
+  return t.defined() ? py::cast(t) : py::none();
+}
+
+// One entry per unit column (row-major file, col); None for a column the
+// file does not have. fixed width: (bytes_u8, validity_or_None); string
+// and list: (offsets_i64, bytes_u8, validity_or_None) — list offsets
+// count ELEMENTS.
+static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
+                            torch::Tensor dicts, torch::Tensor runs,
+                            torch::Tensor soffs, torch::Tensor desc,
+                            int64_t nfiles, int64_t ncols) {
+  std::vector<UnitCol> cols;
+  {
+    py::gil_scoped_release rel;
+    cols = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
+                            nfiles, ncols);
+  }
+  py::list out;
+  for (auto& c : cols) {
+    if (!c.present)
+      out.append(py::none());
+    else if (c.is_string || c.is_list)
+      out.append(py::make_tuple(c.offsets, c.bytes, tensor_or_none(c.validity)));
+    else
+      out.append(py::make_tuple(c.data, tensor_or_none(c.validity)));
+  }
+  return out;
+}
+
+// C++ scan-unit driver (simple path): decode + UseLast merge + gather for
+// one unit entirely from C++ — the python per-unit op storm (GIL-bound)
+// was the scan's critical path. Covers: integer single-PK (int64/int32),
+// every-column UseLast, no CDC, no lists. Python falls back otherwise.
+// Returns one entry per read col (the merged row count is implicit in the
+// tensor sizes):
+//   fixed: [data_u8_gathered, validity_or_None]
+//   string: [offsets_i64, bytes_u8, validity_or_None]
+static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf,
+                                  torch::Tensor dicts, torch::Tensor runs,
+                                  torch::Tensor soffs, torch::Tensor desc,
+                                  int64_t nfiles, int64_t ncols, int64_t pk_ci,
+                                  int64_t pk_es) {
   py::gil_scoped_release rel;  // long device-side section (incl. one sync)
   auto device = vals.device();
   auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(device);
   auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(device);
-  auto da = desc.accessor<int64_t, 2>();
   auto stream = cur_stream();
 
-  torch::Tensor empty_u8 = torch::empty({0}, u8);
-  torch::Tensor runs2 = runs.numel() ? runs.view({-1, 6}) : runs;
-
-  // ---- decode every (file, col) into dense device columns ----
-  // decoded[f][c] = {data_u8 (es per elem), validity_u8 (or undef),
-  //                  offsets_i64/bytes_u8 for strings}
-  struct Col {
-    torch::Tensor data, validity, offsets, bytes;
-    bool is_string = false;
+  auto flat = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
+                               nfiles, ncols);
+  for (auto& c : flat)
+    TORCH_CHECK(c.present && !c.is_list,
+                "scan_unit_uselast: absent or list column (fallback)");
+  auto da = desc.accessor<int64_t, 2>();
+  auto col = [&](int64_t f, int64_t c) -> UnitCol& {
+    return flat[(size_t)(f * ncols + c)];
   };
-  std::vector<std::vector<Col>> cols((size_t)nfiles,
-                                     std::vector<Col>((size_t)ncols));
-  for (int64_t f = 0; f < nfiles; f++) {
-    for (int64_t c = 0; c < ncols; c++) {
-      int64_t u = f * ncols + c;
-      Col& out = cols[f][c];
-      TORCH_CHECK(da[u][0], "scan_unit_uselast: absent column (fallback)");
-      int64_t nv = da[u][4];
-      bool has_null = da[u][8] >= 0 && da[u][5] > 0;
-      torch::Tensor vmask;
-      if (has_null) vmask = validity_buf.narrow(0, da[u][8], nv);
-      if (da[u][1]) {  // string
-        out.is_string = true;
-        out.offsets = soffs.narrow(0, da[u][14], nv + 1);
-        out.bytes = vals.narrow(0, da[u][15], da[u][16]);
-        out.validity = vmask;
-        continue;
-      }
-      int64_t es = da[u][3];
-      if (da[u][2]) {  // dict
-        auto rr = runs2.narrow(0, da[u][11], da[u][12]);
-        // run bit offsets are relative to the whole values buffer (they
-        // already include this chunk's val_off, see read_unit.h)
-        TORCH_CHECK(da[u][6] + da[u][7] <= vals.numel(),
-                    "scan_unit_uselast: dict payload out of range");
-        auto payload = vals;
-        auto idx = torch::empty({da[u][13]}, torch::TensorOptions().dtype(torch::kInt32).device(device));
-        launch_rle_expand(payload.data_ptr<uint8_t>(), rr.data_ptr<int64_t>(),
-                          rr.size(0), idx.data_ptr<int32_t>(), da[u][13], stream);
-        auto dv = dicts.narrow(0, da[u][9], da[u][10]);
-        auto out_d = torch::empty({nv * es}, u8);
-        const uint8_t* vm = has_null ? vmask.data_ptr<uint8_t>() : nullptr;
-        torch::Tensor pos;
-        const int64_t* posp = nullptr;
-        if (has_null) {
-          pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
-          posp = pos.data_ptr<int64_t>();
-        }
-        if (es == 4)
-          launch_dict_gather_scatter<uint32_t>((const uint32_t*)dv.data_ptr(), idx.data_ptr<int32_t>(), vm, posp, (uint32_t*)out_d.data_ptr(), nv, stream);
-        else if (es == 8)
-          launch_dict_gather_scatter<uint64_t>((const uint64_t*)dv.data_ptr(), idx.data_ptr<int32_t>(), vm, posp, (uint64_t*)out_d.data_ptr(), nv, stream);
-        else
-          launch_dict_gather_scatter<uint8_t>(dv.data_ptr<uint8_t>(), idx.data_ptr<int32_t>(), vm, posp, out_d.data_ptr<uint8_t>(), nv, stream);
-        out.data = out_d;
-      } else {
-        auto dense = vals.narrow(0, da[u][6], da[u][7]);
-        if (has_null) {
-          auto pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
-          auto out_d = torch::zeros({nv * es}, u8);
-          if (es == 1)
-            launch_scatter_valid<uint8_t>(dense.data_ptr<uint8_t>(), vmask.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(), out_d.data_ptr<uint8_t>(), nv, stream);
-          else if (es == 2)
-            launch_scatter_valid<uint16_t>((const uint16_t*)dense.data_ptr(), vmask.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(), (uint16_t*)out_d.data_ptr(), nv, stream);
-          else if (es == 4)
-            launch_scatter_valid<uint32_t>((const uint32_t*)dense.data_ptr(), vmask.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(), (uint32_t*)out_d.data_ptr(), nv, stream);
-          else
-            launch_scatter_valid<uint64_t>((const uint64_t*)dense.data_ptr(), vmask.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(), (uint64_t*)out_d.data_ptr(), nv, stream);
-          out.data = out_d;
-        } else {
-          out.data = dense;
-        }
-      }
-      out.validity = vmask;
-    }
-  }
 
   // ---- pack keys per file + pairwise merge-path merges ----
   std::vector<std::pair<torch::Tensor, torch::Tensor>> streams;
   int64_t base = 0;
   for (int64_t f = 0; f < nfiles; f++) {
-    int64_t nv = da[f * ncols + pk_ci][4];
-    auto& pkc = cols[f][pk_ci];
+    int64_t nv = da[f * ncols + pk_ci][UD_NUM_VALUES];
+    auto& pkc = col(f, pk_ci);
     torch::Tensor key64;
     if (pk_es == 8) {
       key64 = pkc.data.view(torch::kInt64);
@@ -553,15 +599,15 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
   std::vector<int64_t> g_col;  // read col index per g_in entry (fixed/validity)
   std::vector<int> g_kind;     // 0=data, 1=validity
   for (int64_t c = 0; c < ncols; c++) {
-    bool is_str = cols[0][c].is_string;
+    bool is_str = col(0, c).is_string;
     bool any_valid = false;
     for (int64_t f = 0; f < nfiles; f++)
-      if (cols[f][c].validity.defined()) any_valid = true;
+      if (col(f, c).validity.defined()) any_valid = true;
     if (!is_str) {
       std::vector<torch::Tensor> parts;
-      int64_t es = da[c][3];
+      int64_t es = da[c][UD_ESIZE];
       for (int64_t f = 0; f < nfiles; f++)
-        parts.push_back(cols[f][c].data.view({-1, es}));
+        parts.push_back(col(f, c).data.view({-1, es}));
       auto cat = nfiles == 1 ? parts[0] : at::cat(parts, 0);
       // gather as typed elements (view to es-wide rows then index)
       g_in.push_back(cat);
@@ -571,9 +617,9 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
     if (any_valid || is_str) {
       std::vector<torch::Tensor> parts;
       for (int64_t f = 0; f < nfiles; f++) {
-        auto v = cols[f][c].validity;
+        auto v = col(f, c).validity;
         if (v.defined()) parts.push_back(v);
-        else parts.push_back(torch::ones({da[f * ncols + c][4]}, u8));
+        else parts.push_back(torch::ones({da[f * ncols + c][UD_NUM_VALUES]}, u8));
       }
       if (any_valid) {
         g_in.push_back(nfiles == 1 ? parts[0] : at::cat(parts, 0));
@@ -590,7 +636,6 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
     while (i < g_in.size()) {
       GatherTable tbl;
       tbl.ncols = 0;
-      size_t start = i;
       for (; i < g_in.size() && tbl.ncols < 16; i++) {
         auto& t = g_in[i];
         int64_t es = t.dim() == 2 ? t.size(1) * t.element_size() : t.element_size();
@@ -603,7 +648,6 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
         g_out[i] = o;
       }
       launch_gather_fixed_multi(tbl, src_idx.data_ptr<int64_t>(), nsurv, stream);
-      (void)start;
     }
   }
   // build outputs per column
@@ -615,7 +659,7 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
   }
   for (int64_t c = 0; c < ncols; c++) {
     std::vector<torch::Tensor> entry;
-    if (!cols[0][c].is_string) {
+    if (!col(0, c).is_string) {
       entry.push_back(col_data[(size_t)c]);
       entry.push_back(col_valid[(size_t)c]);  // may be undefined
     } else {
@@ -624,10 +668,10 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
       int64_t byte_base = 0;
       std::vector<torch::Tensor> adj_offs;
       for (int64_t f = 0; f < nfiles; f++) {
-        auto o = cols[f][c].offsets;
+        auto o = col(f, c).offsets;
         adj_offs.push_back((f == 0 ? o : o + byte_base));
-        bytes_parts.push_back(cols[f][c].bytes);
-        byte_base += cols[f][c].bytes.numel();
+        bytes_parts.push_back(col(f, c).bytes);
+        byte_base += col(f, c).bytes.numel();
       }
       // concatenated offsets: drop leading 0 of subsequent files
       std::vector<torch::Tensor> oparts;
@@ -855,6 +899,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("snappy_decompress", &snappy_decompress);
   m.def("snappy_decompress_into", &snappy_decompress_into);
   m.def("scan_unit_uselast", &scan_unit_uselast);
+  m.def("decode_unit", &decode_unit);
   m.doc() = "lakesoul_amd gfx950 HIP kernels";
   m.def("hash_fixed_column", &hash_fixed_column);
   m.def("hash_string_column", &hash_string_column);

@@ -59,6 +59,19 @@ def np_dtype_for(dtype: str):
     return _NP_DTYPE[dtype]
 
 
+# As stored in parquet: INT32 backs int8/int16 (date32 is int32 and
+# decimals are int64 in the tables above already); decode narrows after.
+_PHYS_INT32 = ("int8", "int16")
+
+
+def torch_phys_dtype_for(dtype: str):
+    return torch.int32 if dtype in _PHYS_INT32 else torch_dtype_for(dtype)
+
+
+def np_phys_dtype_for(dtype: str):
+    return np.int32 if dtype in _PHYS_INT32 else np_dtype_for(dtype)
+
+
 @dataclass
 class Column:
     dtype: str
@@ -113,6 +126,15 @@ class Column:
         if self.is_string:
             raise TypeError("string column: use offsets/bytes")
         return self.data.cpu().numpy()
+
+    def tensors(self):
+        """Every tensor of the column tree (children included)."""
+        for t in (self.data, self.offsets, self.bytes_, self.validity,
+                  self.elem_offsets):
+            if t is not None:
+                yield t
+        for ch in (self.children or {}).values():
+            yield from ch.tensors()
 
     def to_device(self, device) -> "Column":
         # async only when moving TO the GPU: a non_blocking D2H copy into

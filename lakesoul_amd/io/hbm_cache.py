@@ -24,12 +24,8 @@ from .batch import Batch
 
 
 def _batch_bytes(b: Batch) -> int:
-    total = 0
-    for c in b.columns.values():
-        for t in (c.data, c.offsets, c.bytes_, c.validity):
-            if t is not None:
-                total += t.numel() * t.element_size()
-    return total
+    return sum(t.numel() * t.element_size()
+               for c in b.columns.values() for t in c.tensors())
 
 
 class HbmScanCache:

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import os
 import re
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -27,48 +27,40 @@ import torch
 
 from .. import constants
 from ..ops import cpp
-from .batch import Batch, Column
+from .batch import (Batch, Column, np_dtype_for, np_phys_dtype_for,
+                    torch_dtype_for, torch_phys_dtype_for)
 from .filters import decode_stat, resolve_filters
 from .merge_cpu import NpColumn, merge_sorted_files
-from .schema import FIXED_WIDTH_BYTES, Schema
+from .schema import FIXED_WIDTH_BYTES, Schema, map_params, struct_members
 
 _BUCKET_RE = re.compile(r"part-[^/]*_(\d+)\.[a-zA-Z0-9]+$")
 
-_NP_FROM_PHYS = {
-    "bool": np.uint8,
-    "int8": np.int32,
-    "int16": np.int32,
-    "int32": np.int32,
-    "int64": np.int64,
-    "float32": np.float32,
-    "float64": np.float64,
-    "date32": np.int32,
-    "timestamp[us]": np.int64,
-    "timestamp[ms]": np.int64,
-    "timestamp[ns]": np.int64,
-}
 
-def _np_phys(dtype):
-    return np.int64 if dtype.startswith("decimal") else _NP_FROM_PHYS[dtype]
+def _list_row_mask(d: dict, nrow: int):
+    """Row validity of one list chunk, None when it has no null row."""
+    lv = d["list_validity"].numpy()
+    return lv[:nrow] if len(lv) and not lv.all() else None
 
 
-def _np_target(dtype):
-    return np.int64 if dtype.startswith("decimal") else _NP_TARGET[dtype]
-
-
-_NP_TARGET = {
-    "bool": np.uint8,
-    "int8": np.int8,
-    "int16": np.int16,
-    "int32": np.int32,
-    "int64": np.int64,
-    "float32": np.float32,
-    "float64": np.float64,
-    "date32": np.int32,
-    "timestamp[us]": np.int64,
-    "timestamp[ms]": np.int64,
-    "timestamp[ns]": np.int64,
-}
+def _concat_rg_parts(dtype: str, offs_parts, bytes_parts, masks) -> NpColumn:
+    """Concatenate the row-group parts of a variable-width column: offsets
+    rebased, bytes concatenated, validity only if some part has nulls
+    (masks[i] is None for a part without)."""
+    total_rows = sum(len(o) - 1 for o in offs_parts)
+    offs = np.zeros(total_rows + 1, dtype=np.int64)
+    pos, base = 0, 0
+    for o in offs_parts:
+        nr = len(o) - 1
+        offs[pos + 1: pos + nr + 1] = o[1:].astype(np.int64) + base
+        base += int(o[-1]) if len(o) else 0
+        pos += nr
+    bys = np.concatenate(bytes_parts) if bytes_parts else np.empty(0, np.uint8)
+    validity = None
+    if any(m is not None for m in masks):
+        validity = np.concatenate([
+            np.ones(len(o) - 1, dtype=np.uint8) if m is None else m
+            for m, o in zip(masks, offs_parts)])
+    return NpColumn(dtype, None, offs, bys, validity)
 
 
 def extract_hash_bucket_id(path: str) -> Optional[int]:
@@ -134,8 +126,8 @@ class LakeSoulScan:
         # struct/map columns read as their parquet leaves (struct s ->
         # s.a / s.b; map m -> m.key / m.value parallel lists — the same
         # dotted names flatten_element surfaces); the MOR merge runs per
-        # leaf and _np_to_batch reassembles the top-level column
-        from .schema import Field as _LsField, map_params, struct_members
+        # leaf and _to_eval_batch reassembles the top-level column
+        from .schema import Field as _LsField
 
         self._leaf_fields: Dict[str, "object"] = {}
         expanded: List[str] = []
@@ -406,8 +398,8 @@ class LakeSoulScan:
             cur = _torch.cuda.current_stream()
             if batch is not None:
                 for c in batch.columns.values():
-                    for t in (c.data, c.offsets, c.bytes_, c.validity):
-                        if t is not None and t.is_cuda:
+                    for t in c.tensors():
+                        if t.is_cuda:
                             t.record_stream(cur)
             return batch
 
@@ -547,9 +539,7 @@ class LakeSoulScan:
                 return hit
         unit = ScanUnit(unit.partition_desc, unit.bucket_id,
                         self._localize(unit.files), unit.is_compacted_first)
-        needs_merge = bool(self.pk) and (
-            len(unit.files) > 1 or self.cdc_column is not None or bool(self.merge_ops)
-        )
+        needs_merge = self._needs_merge(len(unit.files))
         if oversized and self._chunkable():
             try:
                 return self._read_unit_chunked(unit)
@@ -593,6 +583,11 @@ class LakeSoulScan:
 
             scan_cache().put(cache_key, batch)
         return batch
+
+    def _needs_merge(self, nfiles: int) -> bool:
+        return bool(self.pk) and (
+            nfiles > 1 or self.cdc_column is not None or bool(self.merge_ops)
+        )
 
     def _chunkable(self) -> bool:
         """Chunked (PK-range) merge needs a single primary key whose
@@ -715,10 +710,7 @@ class LakeSoulScan:
             cols, pres = self._read_file_cpu(path, self.read_cols)
             file_cols.append(cols)
             present.append(pres)
-        needs_merge = bool(self.pk) and (
-            len(file_cols) > 1 or self.cdc_column is not None or bool(self.merge_ops)
-        )
-        if needs_merge:
+        if self._needs_merge(len(file_cols)):
             merged = merge_sorted_files(
                 file_cols, self.pk, self.merge_ops, self.cdc_column, present
             )
@@ -735,8 +727,9 @@ class LakeSoulScan:
         return self._np_to_batch(merged, unit)
 
     @staticmethod
-    def _np_col_to_column(dtype: str, npc: NpColumn) -> Column:
-        """Convert one merged NpColumn into a Batch Column."""
+    def _np_leaf_to_column(dtype: str, npc: NpColumn) -> Column:
+        """Wrap one merged NpColumn leaf as a (CPU) Column; list<T> stays
+        the byte-offset binary lane _to_eval_batch converts."""
         validity = (None if npc.validity is None
                     else torch.from_numpy(npc.validity))
         if dtype == "list<string>":
@@ -747,11 +740,12 @@ class LakeSoulScan:
             return Column(dtype, offsets=d["row_offsets"], bytes_=d["bytes"],
                           elem_offsets=d["elem_offsets"], validity=validity)
         if dtype.startswith("list<"):
-            es = np.dtype(_np_phys(dtype[5:-1])).itemsize
-            offs = np.ascontiguousarray(npc.offsets, dtype=np.int64) // es
-            vals = np.ascontiguousarray(npc.bytes_).view(_np_phys(dtype[5:-1]))
-            return Column(dtype, data=torch.from_numpy(vals.copy()),
-                          offsets=torch.from_numpy(offs), validity=validity)
+            return Column(
+                "binary",
+                offsets=torch.from_numpy(
+                    np.ascontiguousarray(npc.offsets, dtype=np.int64)),
+                bytes_=torch.from_numpy(np.ascontiguousarray(npc.bytes_)),
+                validity=validity)
         if npc.is_string:
             return Column(
                 dtype,
@@ -759,69 +753,95 @@ class LakeSoulScan:
                     np.ascontiguousarray(npc.offsets, dtype=np.int32)),
                 bytes_=torch.from_numpy(np.ascontiguousarray(npc.bytes_)),
                 validity=validity)
-        data = npc.data.astype(_np_target(dtype), copy=False)
+        data = npc.data.astype(np_dtype_for(dtype), copy=False)
         return Column(dtype, data=torch.from_numpy(np.ascontiguousarray(data)),
                       validity=validity)
 
     def _np_to_batch(self, merged: Dict[str, NpColumn], unit: ScanUnit) -> Batch:
-        from .schema import map_params, struct_members
+        leaves = {n: self._np_leaf_to_column(self._field_for(n).dtype, c)
+                  for n, c in merged.items()}
+        n = len(next(iter(merged.values()), ()))
+        return self._to_eval_batch(leaves, unit, n, torch.device("cpu"))
+
+    def _to_eval_batch(self, leaves: Dict[str, Column], unit: ScanUnit,
+                       nrows: int, device) -> Batch:
+        """Project the merged leaf columns (any device) to eval_schema:
+        materialize range-partition columns, convert byte-offset list
+        lanes back to element-offset list columns, reassemble struct/map
+        columns from their dotted leaves."""
+
+        def typed(dtype, c):
+            if not dtype.startswith("list<") or dtype == "list<string>":
+                return c   # list<string> is host-decoded to its final form
+            # list<T> lane: the payload is viewed at the PHYSICAL element
+            # width (INT32 backs list<int8>/list<int16>), the unit the
+            # byte offsets were scaled by
+            dt = torch_phys_dtype_for(dtype[5:-1])
+            return Column(dtype,
+                          data=(c.bytes_.view(dt) if c.bytes_.numel()
+                                else torch.empty(0, dtype=dt, device=device)),
+                          offsets=c.offsets.to(torch.int64) // dt.itemsize,
+                          validity=c.validity)
+
+        def nested(f, members):
+            # merge ran per leaf and row alignment is shared, so the
+            # row validity is the first member's that has one; members
+            # carry none
+            kids = {mn: typed(mt, leaves[f"{f.name}.{mn}"])
+                    for mn, mt in members}
+            validity = next((k.validity for k in kids.values()
+                             if k.validity is not None), None)
+            return Column(f.dtype, validity=validity,
+                          children={mn: replace(k, validity=None)
+                                    for mn, k in kids.items()})
 
         cols: Dict[str, Column] = {}
         for f in self.eval_schema:
-            if f.name in self.range_cols:
-                cols[f.name] = self._range_value_column(f, unit, merged)
-                continue
             sm = struct_members(f.dtype)
             mp = map_params(f.dtype)
-            if sm is not None:
-                # reassemble from the dotted leaves (merge ran per leaf;
-                # row alignment is shared, so the struct validity is any
-                # member's validity)
-                kids, validity = {}, None
-                for mn, mt in sm:
-                    mc = self._np_col_to_column(mt, merged[f"{f.name}.{mn}"])
-                    validity = mc.validity if validity is None else validity
-                    mc.validity = None
-                    kids[mn] = mc
-                cols[f.name] = Column(f.dtype, validity=validity, children=kids)
-                continue
-            if mp is not None:
-                kt, vt = mp
-                kc = self._np_col_to_column(f"list<{kt}>",
-                                            merged[f"{f.name}.key"])
-                vc = self._np_col_to_column(f"list<{vt}>",
-                                            merged[f"{f.name}.value"])
-                validity = kc.validity
-                kc.validity = vc.validity = None
-                cols[f.name] = Column(f.dtype, validity=validity,
-                                      children={"key": kc, "value": vc})
-                continue
-            cols[f.name] = self._np_col_to_column(f.dtype, merged[f.name])
+            if f.name in self.range_cols:
+                cols[f.name] = self._range_column(f, unit, nrows, device)
+            elif sm is not None:
+                cols[f.name] = nested(f, sm)
+            elif mp is not None:
+                cols[f.name] = nested(f, (("key", f"list<{mp[0]}>"),
+                                          ("value", f"list<{mp[1]}>")))
+            else:
+                cols[f.name] = typed(f.dtype, leaves[f.name])
         return Batch(self.eval_schema, cols)
 
-    def _range_value_column(self, f, unit: ScanUnit, merged) -> Column:
+    @staticmethod
+    def _range_column(f, unit: ScanUnit, n: int, device) -> Column:
         """Materialize a range-partition column from the partition_desc.
 
         Values are sentinel-decoded (NULL/''/','/'=' round trip —
         reference helpers/mod.rs:325); the NULL sentinel materializes as
         an all-null column."""
-        n = len(next(iter(merged.values())))
         val, found = None, False
         for kv in unit.partition_desc.split(","):
             if "=" in kv and kv.split("=", 1)[0] == f.name:
                 val = constants.decode_partition_value(kv.split("=", 1)[1])
                 found = True
         is_null = found and val is None
-        validity = (torch.zeros(n, dtype=torch.uint8) if is_null else None)
+        validity = (torch.zeros(n, dtype=torch.uint8, device=device)
+                    if is_null else None)
         if f.is_fixed_width:
-            npdt = _np_target(f.dtype)
-            arr = np.full(n, npdt(val) if (found and not is_null) else 0, dtype=npdt)
-            return Column(f.dtype, data=torch.from_numpy(arr), validity=validity)
+            if not found or is_null:
+                x = 0
+            else:
+                x = float(val) if f.dtype.startswith("float") else int(val)
+            return Column(f.dtype, validity=validity,
+                          data=torch.full((n,), x, device=device,
+                                          dtype=torch_dtype_for(f.dtype)))
         enc = (val or "").encode()
-        offs = np.arange(n + 1, dtype=np.int32) * len(enc)
-        bys = np.frombuffer(enc * n, dtype=np.uint8).copy() if n else np.empty(0, np.uint8)
-        return Column(f.dtype, offsets=torch.from_numpy(offs),
-                      bytes_=torch.from_numpy(bys), validity=validity)
+        # string offsets are int32 on the host, int64 in HBM (as the
+        # decoders of either path produce them)
+        odt = torch.int64 if torch.device(device).type == "cuda" else torch.int32
+        offs = torch.arange(n + 1, dtype=odt, device=device) * len(enc)
+        bys = (torch.frombuffer(bytearray(enc * n), dtype=torch.uint8).to(device)
+               if n and enc
+               else torch.empty(0, dtype=torch.uint8, device=device))
+        return Column(f.dtype, offsets=offs, bytes_=bys, validity=validity)
 
     def _read_file_cpu(self, path: str, names: Sequence[str],
                        rg_subset: Optional[Sequence[int]] = None) -> Dict[str, NpColumn]:
@@ -851,7 +871,6 @@ class LakeSoulScan:
                     # opaque whole-row gather keeps element boundaries;
                     # split_len_prefixed() parses it back at the end
                     offs_parts, bytes_parts, masks = [], [], []
-                    any_null = False
                     for rg in rg_iter:
                         d = chunks[ci]
                         ci += 1
@@ -874,95 +893,54 @@ class LakeSoulScan:
                                 out_b[dst] = by[:nb_]
                         offs_parts.append(new_eoffs[lo_])
                         bytes_parts.append(out_b)
-                        lv = d["list_validity"].numpy()
-                        nrow = len(offs_parts[-1]) - 1
-                        if len(lv) and not lv.all():
-                            any_null = True
-                            masks.append(lv[:nrow])
-                        else:
-                            masks.append(np.ones(nrow, dtype=np.uint8))
-                    validity = np.concatenate(masks) if any_null else None
-                    total_rows = sum(len(o) - 1 for o in offs_parts)
-                    offs = np.zeros(total_rows + 1, dtype=np.int64)
-                    pos, base = 0, 0
-                    for o in offs_parts:
-                        nr = len(o) - 1
-                        offs[pos + 1: pos + nr + 1] = o[1:] + base
-                        base += int(o[-1]) if len(o) else 0
-                        pos += nr
-                    bys = (np.concatenate(bytes_parts) if bytes_parts
-                           else np.empty(0, np.uint8))
-                    out[name] = NpColumn(f.dtype, None, offs, bys, validity)
+                        masks.append(_list_row_mask(d, len(lo_) - 1))
+                    out[name] = _concat_rg_parts(f.dtype, offs_parts,
+                                                 bytes_parts, masks)
                     continue
                 if f.dtype.startswith("list<"):
                     # list<T> rides the byte-string machinery downstream:
                     # offsets in BYTES over the raw element buffer (merge/
                     # gather treat the whole list value opaquely — UseLast
                     # whole-value semantics, reference merge/mod.rs:65-89)
-                    es = np.dtype(_np_phys(f.dtype[5:-1])).itemsize
+                    es = np.dtype(np_phys_dtype_for(f.dtype[5:-1])).itemsize
                     offs_parts, bytes_parts, masks = [], [], []
-                    any_null = False
                     for rg in rg_iter:
                         d = chunks[ci]
                         ci += 1
                         offs_parts.append(d["list_offsets"].numpy() * es)
                         bytes_parts.append(d["data"].numpy())
-                        lv = d["list_validity"].numpy()
-                        nrow = len(offs_parts[-1]) - 1
-                        if len(lv) and not lv.all():
-                            any_null = True
-                            masks.append(lv[:nrow])
-                        else:
-                            masks.append(np.ones(nrow, dtype=np.uint8))
-                    validity = np.concatenate(masks) if any_null else None
-                    total_rows = sum(len(o) - 1 for o in offs_parts)
-                    offs = np.zeros(total_rows + 1, dtype=np.int64)
-                    pos, base = 0, 0
-                    for o in offs_parts:
-                        nr = len(o) - 1
-                        offs[pos + 1: pos + nr + 1] = o[1:].astype(np.int64) + base
-                        base += int(o[-1]) if len(o) else 0
-                        pos += nr
-                    bys = (np.concatenate(bytes_parts) if bytes_parts
-                           else np.empty(0, np.uint8))
-                    out[name] = NpColumn(f.dtype, None, offs, bys, validity)
+                        masks.append(_list_row_mask(d, len(offs_parts[-1]) - 1))
+                    out[name] = _concat_rg_parts(f.dtype, offs_parts,
+                                                 bytes_parts, masks)
                     continue
-                parts, offs_parts, bytes_parts, masks = [], [], [], []
+                if f.dtype in ("string", "binary"):
+                    offs_parts, bytes_parts, masks = [], [], []
+                    for rg in rg_iter:
+                        d = chunks[ci]
+                        ci += 1
+                        offs_parts.append(d["offsets"].numpy())
+                        bytes_parts.append(d["bytes"].numpy())
+                        v = d["validity"].numpy()
+                        masks.append(v if len(v) else None)
+                    out[name] = _concat_rg_parts(f.dtype, offs_parts,
+                                                 bytes_parts, masks)
+                    continue
+                phys = np_phys_dtype_for(f.dtype)
+                parts, masks = [], []
                 any_null = False
                 for rg in rg_iter:
                     d = chunks[ci]
                     ci += 1
-                    nv = d["num_values"]
-                    if f.dtype in ("string", "binary"):
-                        offs_parts.append(d["offsets"].numpy())
-                        bytes_parts.append(d["bytes"].numpy())
-                    else:
-                        parts.append(d["data"].numpy().view(_np_phys(f.dtype)))
+                    parts.append(d["data"].numpy().view(phys))
                     v = d["validity"].numpy()
                     if len(v):
                         any_null = True
                         masks.append(v)
                     else:
-                        masks.append(np.ones(nv, dtype=np.uint8))
+                        masks.append(np.ones(d["num_values"], dtype=np.uint8))
                 validity = np.concatenate(masks) if any_null else None
-                if f.dtype in ("string", "binary"):
-                    total_rows = sum(len(o) - 1 for o in offs_parts)
-                    offs = np.zeros(total_rows + 1, dtype=np.int64)
-                    pos, base = 0, 0
-                    for o in offs_parts:
-                        n = len(o) - 1
-                        offs[pos + 1 : pos + n + 1] = o[1:].astype(np.int64) + base
-                        base += int(o[-1]) if len(o) else 0
-                        pos += n
-                    bys = (
-                        np.concatenate(bytes_parts)
-                        if bytes_parts
-                        else np.empty(0, np.uint8)
-                    )
-                    out[name] = NpColumn(f.dtype, None, offs, bys, validity)
-                else:
-                    data = np.concatenate(parts) if parts else np.empty(0, _np_phys(f.dtype))
-                    out[name] = NpColumn(f.dtype, data, None, None, validity)
+                data = np.concatenate(parts) if parts else np.empty(0, phys)
+                out[name] = NpColumn(f.dtype, data, None, None, validity)
             # schema evolution: missing columns become nulls
             for name in names:
                 if name in out:
@@ -979,7 +957,7 @@ class LakeSoulScan:
                 else:
                     out[name] = NpColumn(
                         f.dtype,
-                        np.zeros(total, dtype=_np_phys(f.dtype)),
+                        np.zeros(total, dtype=np_phys_dtype_for(f.dtype)),
                         None,
                         None,
                         np.zeros(total, dtype=np.uint8),

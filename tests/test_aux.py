@@ -294,3 +294,54 @@ def test_memprof_snapshot_and_track(capsys):
         buf = bytearray(50 * 1024 * 1024)
         assert len(buf) == 50 * 1024 * 1024
     assert len(msgs) == 1 and "alloc-test" in msgs[0]
+
+
+def test_column_tensors_walks_whole_tree():
+    """Column.tensors() yields exactly the tensors reachable by hand from
+    the column tree (elem_offsets and every child included), and the scan
+    cache sizes a batch from the same walk."""
+    import torch
+
+    from lakesoul_amd.io.batch import Batch
+    from lakesoul_amd.io.hbm_cache import _batch_bytes
+
+    schema = Schema([
+        Field("x", "int32"), Field("s", "string"), Field("l", "list<int64>"),
+        Field("ls", "list<string>"),
+        Field("st", "struct<a:int64,b:string>"),
+        Field("m", "map<string,int64>"),
+    ])
+    b = Batch.from_dict({
+        "x": np.arange(3, dtype=np.int32),
+        "s": ["a", None, "ccc"],
+        "l": [[1, 2], None, [3]],
+        "ls": [["p", "qq"], [], None],
+        "st": [{"a": 1, "b": "u"}, None, {"a": 3, "b": "www"}],
+        "m": [{"k": 1}, {"k2": 2, "k3": 3}, None],
+    }, schema)
+    c = b.columns
+    c["x"].validity = torch.tensor([1, 0, 1], dtype=torch.uint8)
+    st, m = c["st"], c["m"]
+    assert st.validity is not None and m.validity is not None
+    by_hand = {
+        "x": [c["x"].data, c["x"].validity],
+        "s": [c["s"].offsets, c["s"].bytes_, c["s"].validity],
+        "l": [c["l"].data, c["l"].offsets, c["l"].validity],
+        "ls": [c["ls"].offsets, c["ls"].bytes_, c["ls"].validity,
+               c["ls"].elem_offsets],
+        "st": [st.validity, st.children["a"].data,
+               st.children["b"].offsets, st.children["b"].bytes_],
+        "m": [m.validity,
+              m.children["key"].offsets, m.children["key"].bytes_,
+              m.children["key"].elem_offsets,
+              m.children["value"].data, m.children["value"].offsets],
+    }
+    total = 0
+    for name, want in by_hand.items():
+        assert all(t is not None for t in want), name
+        got = list(c[name].tensors())
+        assert sorted(t.data_ptr() for t in got) == \
+            sorted(t.data_ptr() for t in want), name
+        assert len(got) == len(want), name
+        total += sum(t.numel() * t.element_size() for t in want)
+    assert _batch_bytes(b) == total

@@ -91,35 +91,49 @@ def test_merge_pairs_kernel(dev):
     np.testing.assert_array_equal(keys, ref)
 
 
-def test_rle_dict_decode_gpu_vs_pyarrow(dev, tmp_path):
+@pytest.mark.parametrize("stored", ["int64", "int32", "float64"])
+def test_rle_dict_decode_gpu_vs_pyarrow(dev, tmp_path, stored):
+    """Dictionary chunks through the production decoder (read_unit_raw ->
+    UnitTransfer -> decode_unit). A PLAIN column precedes the dictionary
+    column, so the dict payload sits at a non-zero offset of the values
+    buffer; es = 4 and 8 both take the dict path."""
     import pyarrow as pa
     import pyarrow.parquet as pq
 
+    from lakesoul_amd.io.reader_gpu import UnitTransfer
     from lakesoul_amd.ops import cpp, hip
 
     n = 50000
     rng = np.random.default_rng(2)
     cat = (rng.integers(0, 100, n) * 7).astype(np.int64)
-    vals = [None if rng.random() < 0.1 else int(cat[i]) for i in range(n)]
-    tbl = pa.table({"c": pa.array(vals, type=pa.int64())})
+    conv = float if stored == "float64" else int
+    vals = [None if rng.random() < 0.1 else conv(cat[i]) for i in range(n)]
+    pa_type = {"int64": pa.int64(), "int32": pa.int32(),
+               "float64": pa.float64()}[stored]
+    tbl = pa.table({"a": pa.array(np.arange(n, dtype=np.int64)),
+                    "c": pa.array(vals, type=pa_type)})
     path = tmp_path / "dict.parquet"
-    pq.write_table(tbl, str(path), use_dictionary=True, compression="zstd", row_group_size=20000)
+    pq.write_table(tbl, str(path), use_dictionary=["c"], compression="zstd",
+                   row_group_size=20000)
+    assert pq.ParquetFile(str(path)).metadata.num_row_groups == 3
 
-    h = cpp().open_parquet(str(path))
-    meta = cpp().parquet_meta(h)
-    outs = []
-    for rg in range(meta["num_row_groups"]):
-        d = cpp().read_chunk_raw(h, rg, 0)
-        assert d["is_dict"]
-        from lakesoul_amd.io.reader_gpu import _decode_fixed_chunk_gpu
-
-        col = _decode_fixed_chunk_gpu(d, "int64", dev)
-        got = col.data.cpu().numpy()
-        mask = col.validity.cpu().numpy() if col.validity is not None else np.ones(len(got), np.uint8)
-        outs.append((got, mask))
-    cpp().close_parquet(h)
-    got = np.concatenate([o[0] for o in outs])
-    mask = np.concatenate([o[1] for o in outs])
+    raw = cpp().read_unit_raw([str(path)], ["a", "c"], 0, False)
+    tr = UnitTransfer(raw, dev)
+    assert tr.dicts is not None and tr.runs is not None  # c is dict-encoded
+    e_u8 = torch.empty(0, dtype=torch.uint8, device=dev)
+    e_i64 = torch.empty(0, dtype=torch.int64, device=dev)
+    outs = hip().decode_unit(
+        tr.vals, tr.validity if tr.validity is not None else e_u8, tr.dicts,
+        tr.runs, tr.soffs if tr.soffs is not None else e_i64, raw["desc"], 1, 2)
+    assert len(outs) == 2
+    a_bytes, a_valid = outs[0]
+    assert a_valid is None
+    np.testing.assert_array_equal(
+        a_bytes.view(torch.int64).cpu().numpy(), np.arange(n))
+    c_bytes, c_valid = outs[1]
+    got = c_bytes.view(getattr(torch, stored)).cpu().numpy()
+    mask = c_valid.cpu().numpy()
+    assert len(got) == n and len(mask) == n
     for i in range(n):
         if vals[i] is None:
             assert mask[i] == 0
@@ -164,31 +178,40 @@ def test_end_to_end_gpu_scan_matches_cpu(dev, tmp_path):
     t = catalog.create_table(
         "gput",
         Schema([Field("id", "int64", False), Field("v", "float64"),
-                Field("k", "int32"), Field("s", "string")]),
+                Field("k", "int32"), Field("s", "string"),
+                Field("f", "bool")]),
         primary_keys=["id"],
         hash_bucket_num=4,
     )
     n = 100000
+    import pyarrow as pa
+
     rng = np.random.default_rng(4)
+    # nullable bool: the es = 1 null-scatter of the decoder
+    flags = pa.array([None if i % 5 == 0 else i % 3 == 0 for i in range(n)],
+                     type=pa.bool_())
     # write on GPU (GPU murmur3 + GPU sort)
     t.upsert(
-        {
+        pa.table({
             "id": np.arange(n, dtype=np.int64),
             "v": rng.normal(size=n),
             "k": rng.integers(0, 100, n, dtype=np.int32),
             "s": [f"s{i}" for i in range(n)],
-        },
+            "f": flags,
+        }),
         device="cuda",
     )
     for it in range(3):
         ids = rng.choice(n, 5000, replace=False).astype(np.int64)
         t.upsert(
-            {
+            pa.table({
                 "id": ids,
                 "v": np.full(5000, float(it)),
                 "k": np.full(5000, it, dtype=np.int32),
                 "s": [f"u{it}"] * 5000,
-            },
+                "f": pa.array([None, True, False, None, True] * 1000,
+                              type=pa.bool_()),
+            }),
             device="cuda",
         )
     cpu_df = (
@@ -201,6 +224,7 @@ def test_end_to_end_gpu_scan_matches_cpu(dev, tmp_path):
 
     pd.testing.assert_frame_equal(cpu_df, gpu_df)
     assert len(gpu_df) == n
+    assert gpu_df["f"].isna().any() and gpu_df["f"].eq(True).any()
 
 
 def test_gpu_merge_operators_match_cpu(dev, tmp_path):
@@ -642,6 +666,31 @@ def test_gpu_list_column_mor(dev, tmp_path):
             np.testing.assert_allclose(list(b), list(a), err_msg=str(i))
     np.testing.assert_allclose(gpu["v"].to_numpy(), cpu["v"].to_numpy())
     np.testing.assert_allclose(list(gpu["emb"].iloc[3]), [9.0])
+
+    # list<int16>: stored at the physical INT32 width; values include
+    # negatives and magnitudes above 255
+    t16 = catalog.create_table(
+        "gl16",
+        Schema([Field("id", "int64", False), Field("w", "list<int16>")]),
+        primary_keys=["id"], hash_bucket_num=1,
+    )
+    m = 64
+    want = [None if i % 7 == 0 else
+            [(-1) ** j * (300 * i + 7 * j) for j in range(i % 5)]
+            for i in range(m)]
+    t16.upsert({"id": np.arange(m, dtype=np.int64), "w": want})
+    t16.upsert({"id": np.array([3, 8], dtype=np.int64),
+                "w": [[-32768, 32767, 256], None]})
+    want[3], want[8] = [-32768, 32767, 256], None
+    cpu = t16.scan(device="cpu").to_arrow().to_pandas().sort_values("id").reset_index(drop=True)
+    gpu = t16.scan(device="cuda").to_arrow().to_pandas().sort_values("id").reset_index(drop=True)
+    assert len(cpu) == m and len(gpu) == m
+    for i in range(m):
+        for got in (cpu["w"].iloc[i], gpu["w"].iloc[i]):
+            if want[i] is None:
+                assert got is None, i
+            else:
+                assert list(got) == want[i], i
 
 
 def test_gpu_list_string_scan(dev, tmp_path):
