@@ -15,6 +15,8 @@
 
 #include <cstdint>
 
+#include "kernels.h"
+
 namespace lakesoul {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;

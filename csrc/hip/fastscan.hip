@@ -22,53 +22,11 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "kernels.h"
+
 namespace lakesoul {
 
-// bits: [m][w] uint8; lut: [nq][g*16] f32; out: [m][nq] f32
-__global__ __launch_bounds__(256) void fastscan_lut_kernel(
-    const uint8_t* __restrict__ bits, const float* __restrict__ lut,
-    float* __restrict__ out, int64_t m, int32_t nq, int32_t w, int32_t g) {
-  extern __shared__ float slut[];  // g*16 floats
-  int q = (int)blockIdx.y;
-  const float* lq = lut + (int64_t)q * g * 16;
-  for (int i = (int)threadIdx.x; i < g * 16; i += (int)blockDim.x)
-    slut[i] = lq[i];
-  __syncthreads();
-  int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  const uint8_t* bp = bits + row * (int64_t)w;
-  float acc = 0.f;
-  int b = 0;
-  // 4-byte chunks through a single dword load
-  for (; b + 4 <= w; b += 4) {
-    uint32_t v4;
-    __builtin_memcpy(&v4, bp + b, 4);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      uint32_t byte = (v4 >> (8 * j)) & 0xFF;
-      acc += slut[(2 * (b + j)) * 16 + (byte & 0xF)];
-      int g2 = 2 * (b + j) + 1;
-      if (g2 < g) acc += slut[g2 * 16 + (byte >> 4)];
-    }
-  }
-  for (; b < w; b++) {
-    uint32_t byte = bp[b];
-    acc += slut[(2 * b) * 16 + (byte & 0xF)];
-    int g2 = 2 * b + 1;
-    if (g2 < g) acc += slut[g2 * 16 + (byte >> 4)];
-  }
-  out[row * (int64_t)nq + q] = acc;
-}
-
-void launch_fastscan_lut(const uint8_t* bits, const float* lut,
-                                    float* out, int64_t m, int32_t nq,
-                                    int32_t w, int32_t g, hipStream_t s) {
-  dim3 grid((uint32_t)((m + 255) / 256), (uint32_t)nq);
-  size_t lds = (size_t)g * 16 * sizeof(float);
-  hipLaunchKernelGGL(fastscan_lut_kernel, grid, dim3(256), lds, s, bits, lut,
-                     out, m, nq, w, g);
-}
-
+// bits: [m][w] uint8; lut: [nq][g*16] f32.
 // Fused stage-1 estimator: the LUT accumulate PLUS the RaBitQ
 // correction factors applied in-register, writing the estimated
 // distance directly (est[q][row] = f_add[row] + g_add[q][cl(row)] +
@@ -226,48 +184,14 @@ void launch_fastscan_est(const uint8_t* bits, const float* lut,
                      w, g, n_clusters);
 }
 
-// Ex-code refinement dot: ex nibbles [m][wn] uint8 (wn = ceil(dim/2),
-// low nibble = even dim), q: [nq][dim] f32 -> out [m][nq] f32 of
-// <ex_code, q>. Candidate sets are small (top-C per query), so a simple
-// one-thread-per-(row) loop with q staged in LDS suffices.
-__global__ __launch_bounds__(256) void fastscan_ex_dot_kernel(
-    const uint8_t* __restrict__ ex, const float* __restrict__ qv,
-    float* __restrict__ out, int64_t m, int32_t nq, int32_t wn,
-    int32_t dim) {
-  extern __shared__ float sq[];  // dim floats for this block's query
-  int q = (int)blockIdx.y;
-  const float* qp = qv + (int64_t)q * dim;
-  for (int i = (int)threadIdx.x; i < dim; i += (int)blockDim.x) sq[i] = qp[i];
-  __syncthreads();
-  int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  const uint8_t* ep = ex + row * (int64_t)wn;
-  float acc = 0.f;
-  for (int b = 0; b < wn; b++) {
-    uint32_t v = ep[b];
-    int d0 = 2 * b;
-    acc += (float)(v & 0xF) * sq[d0];
-    if (d0 + 1 < dim) acc += (float)(v >> 4) * sq[d0 + 1];
-  }
-  out[row * (int64_t)nq + q] = acc;
-}
-
-void launch_fastscan_ex_dot(const uint8_t* ex, const float* qv,
-                                       float* out, int64_t m, int32_t nq,
-                                       int32_t wn, int32_t dim,
-                                       hipStream_t s) {
-  dim3 grid((uint32_t)((m + 255) / 256), (uint32_t)nq);
-  size_t lds = (size_t)dim * sizeof(float);
-  hipLaunchKernelGGL(fastscan_ex_dot_kernel, grid, dim3(256), lds, s, ex, qv,
-                     out, m, nq, wn, dim);
-}
-
-// Pair-wise ex dots: one dot per (query, candidate) pair instead of
-// (unique-candidate x every-query). At C candidates/query the unique-row
-// variant above does ~nq/overlap times the needed work (measured 93 ms
-// of 123 ms in the 5Mx768 hi-C search); this form reads each packed ex
-// row once per selecting query only. Block = one query's chunk of
-// candidates; the query vector stages through LDS.
+// Ex-code refinement dots: ex nibbles [n][wn] uint8 (wn = ceil(dim/2),
+// low nibble = even dim), q: [nq][dim] f32. One dot per (query,
+// candidate) pair instead of (unique-candidate x every-query): at C
+// candidates/query the unique-row form this replaced did ~nq/overlap
+// times the needed work (measured 93 ms of 123 ms in the 5Mx768 hi-C
+// search); this form reads each packed ex row once per selecting query
+// only. Block = one query's chunk of candidates; the query vector stages
+// through LDS.
 __global__ __launch_bounds__(256) void fastscan_ex_dot_pairs_kernel(
     const uint8_t* __restrict__ ex, const int64_t* __restrict__ cand,
     const float* __restrict__ qv, float* __restrict__ out, int32_t C,

@@ -6,60 +6,9 @@
 #include <c10/hip/HIPStream.h>
 
 #include "../cpp/unit_desc.h"
+#include "kernels.h"
 
 namespace py = pybind11;
-
-namespace lakesoul {
-
-struct GatherTable {
-  const void* src[16];
-  void* dst[16];
-  int esize[16];
-  int ncols;
-};
-
-void launch_hash_fixed(int dt, const void*, const uint8_t*, const int64_t*, int64_t*, int64_t, int, hipStream_t);
-void launch_hash_string(const int32_t*, const uint8_t*, const uint8_t*, const int64_t*, int64_t*, int64_t, int, hipStream_t);
-void launch_bucket_ids(const int64_t*, int32_t*, int64_t, uint32_t, hipStream_t);
-void launch_rle_expand(const uint8_t*, const int64_t*, int64_t, int32_t*, int64_t, hipStream_t);
-template <typename T>
-void launch_dict_gather_scatter(const T*, const int32_t*, const uint8_t*, const int64_t*, T*, int64_t, hipStream_t);
-template <typename T>
-void launch_scatter_valid(const T*, const uint8_t*, const int64_t*, T*, int64_t, hipStream_t);
-void launch_merge_pairs(const uint64_t*, const uint64_t*, int64_t, const uint64_t*, const uint64_t*, int64_t, uint64_t*, uint64_t*, hipStream_t);
-void launch_keep_last(const uint64_t*, uint8_t*, int64_t, hipStream_t);
-void launch_group_start(const uint64_t*, uint8_t*, int64_t, hipStream_t);
-void launch_pack_key_i64(const int64_t*, uint64_t*, int64_t, hipStream_t);
-void launch_pack_key_2xi32(const int32_t*, const int32_t*, uint64_t*, int64_t, hipStream_t);
-void launch_gather_fixed_multi(const GatherTable&, const int64_t*, int64_t, hipStream_t);
-void launch_gather_strings(const uint8_t*, const int64_t*, const int64_t*, const int64_t*, uint8_t*, int64_t, hipStream_t);
-void launch_bytes_ne_mask(const int64_t*, const uint8_t*, const uint8_t*, int, uint8_t*, int64_t, hipStream_t);
-template <typename T, typename ACC>
-void launch_segmented_sum(const T*, const int64_t*, const uint8_t*, const uint8_t*, ACC*, int32_t*, int64_t, hipStream_t);
-void launch_segmented_last(const int64_t*, const uint8_t*, const uint8_t*, int64_t*, int64_t, hipStream_t);
-void launch_hamming_scores(const uint64_t*, const uint64_t*, int32_t*, int64_t,
-                           int, int, hipStream_t);
-void launch_str_chunk_keys(const int64_t*, const uint8_t*, int64_t, int64_t*,
-                           int64_t, hipStream_t);
-void launch_ann_scores(const short*, const short*, float*, int64_t, int32_t, int32_t, hipStream_t);
-void launch_ann_scores_t(const short*, const short*, float*, int64_t, int32_t, int32_t, hipStream_t);
-void launch_fastscan_lut(const uint8_t*, const float*, float*, int64_t,
-                         int32_t, int32_t, int32_t, hipStream_t);
-void launch_fastscan_ex_dot(const uint8_t*, const float*, float*, int64_t,
-                            int32_t, int32_t, int32_t, hipStream_t);
-void launch_fastscan_ex_dot_pairs(const uint8_t*, const int64_t*,
-                                  const float*, float*, int32_t, int32_t,
-                                  int32_t, int32_t, hipStream_t);
-void launch_fastscan_est(const uint8_t*, const float*, const float*,
-                         const float*, const int32_t*, const float*,
-                         const float*, float*, int64_t, int32_t, int32_t,
-                         int32_t, int32_t, hipStream_t);
-void launch_snappy_decompress(const uint8_t*, const int64_t*, int64_t, uint8_t*, int32_t*, hipStream_t);
-void launch_zstd_decompress(const uint8_t*, const int64_t*, int64_t, uint8_t*,
-                            uint8_t*, int64_t, int32_t*, hipStream_t);
-int64_t lsz_gpu_litbuf_bytes();
-
-}  // namespace lakesoul
 
 using namespace lakesoul;
 
@@ -136,16 +85,7 @@ static torch::Tensor bucket_ids(torch::Tensor hashes, int64_t nbuckets) {
 
 // ---- decode ----------------------------------------------------------- //
 
-static torch::Tensor rle_expand(torch::Tensor payload, torch::Tensor runs, int64_t n) {
-  CHECK_GPU(payload);
-  CHECK_GPU(runs);
-  auto out = torch::empty({n}, payload.options().dtype(torch::kInt32));
-  launch_rle_expand(payload.data_ptr<uint8_t>(), runs.data_ptr<int64_t>(),
-                    runs.size(0), out.data_ptr<int32_t>(), n, cur_stream());
-  return out;
-}
-
-// element-size dispatch, written once for the bindings and decode_unit
+// element-size dispatch for decode_unit_cols
 static void dict_gather_scatter_es(int64_t es, const void* dict_vals,
                                    const int32_t* idx, const uint8_t* vmask,
                                    const int64_t* pos, void* out, int64_t n,
@@ -175,58 +115,47 @@ static void scatter_valid_es(int64_t es, const void* dense, const uint8_t* vmask
     TORCH_CHECK(false, "scatter_valid: unsupported elem size ", es);
 }
 
-static torch::Tensor dict_gather_scatter(torch::Tensor dict_vals, torch::Tensor idx,
-                                         torch::Tensor validity, torch::Tensor positions,
-                                         int64_t elem_size, int64_t n) {
-  CHECK_GPU_NONEMPTY(validity);
-  CHECK_GPU_NONEMPTY(positions);
-  CHECK_GPU(dict_vals);
-  CHECK_GPU(idx);
-  auto out = torch::empty({n * elem_size}, dict_vals.options().dtype(torch::kUInt8));
-  dict_gather_scatter_es(
-      elem_size, dict_vals.data_ptr(), idx.data_ptr<int32_t>(), opt_u8(validity),
-      validity.numel() ? positions.data_ptr<int64_t>() : nullptr, out.data_ptr(),
-      n, cur_stream());
-  return out;
-}
-
-static torch::Tensor scatter_valid(torch::Tensor dense, torch::Tensor validity,
-                                   torch::Tensor positions, int64_t elem_size,
-                                   int64_t n) {
-  CHECK_GPU_NONEMPTY(validity);
-  CHECK_GPU_NONEMPTY(positions);
-  CHECK_GPU(dense);
-  auto out = torch::zeros({n * elem_size}, dense.options().dtype(torch::kUInt8));
-  scatter_valid_es(elem_size, dense.data_ptr(), validity.data_ptr<uint8_t>(),
-                   positions.data_ptr<int64_t>(), out.data_ptr(), n, cur_stream());
-  return out;
-}
-
 // ---- merge ------------------------------------------------------------ //
 
-static std::vector<torch::Tensor> merge_pairs(torch::Tensor kA, torch::Tensor vA,
-                                              torch::Tensor kB, torch::Tensor vB) {
-  CHECK_GPU_NONEMPTY(vA);
-  CHECK_GPU_NONEMPTY(vB);
-  CHECK_GPU(kA);
-  CHECK_GPU(kB);
-  int64_t nA = kA.numel(), nB = kB.numel();
-  auto kOut = torch::empty({nA + nB}, kA.options());
-  auto vOut = torch::empty({nA + nB}, vA.options());
-  launch_merge_pairs((const uint64_t*)kA.data_ptr(), (const uint64_t*)vA.data_ptr(), nA,
-                     (const uint64_t*)kB.data_ptr(), (const uint64_t*)vB.data_ptr(), nB,
-                     (uint64_t*)kOut.data_ptr(), (uint64_t*)vOut.data_ptr(),
-                     cur_stream());
-  return {kOut, vOut};
-}
-
-static torch::Tensor keep_last_mask(torch::Tensor keys) {
-  CHECK_GPU(keys);
-  int64_t n = keys.numel();
-  auto out = torch::empty({n}, keys.options().dtype(torch::kUInt8));
-  launch_keep_last((const uint64_t*)keys.data_ptr(), out.data_ptr<uint8_t>(), n,
-                   cur_stream());
-  return out;
+// K sorted streams of packed u64 keys (int64 storage) -> (keys, order):
+// the merged keys and, per merged row, its index in the concatenation of
+// the streams in input order. Pairwise merge-path passes, an odd stream
+// carried forward; on equal keys the earlier (older) stream comes first.
+static std::pair<torch::Tensor, torch::Tensor> merge_key_streams(
+    std::vector<torch::Tensor> keys) {
+  TORCH_CHECK(!keys.empty(), "merge_sorted_keys: no streams");
+  std::vector<torch::Tensor> rows;
+  int64_t base = 0;
+  for (auto& k : keys) {
+    CHECK_GPU(k);
+    TORCH_CHECK(k.scalar_type() == torch::kInt64 && k.dim() == 1,
+                "merge_sorted_keys: keys must be 1-d int64");
+    rows.push_back(torch::arange(base, base + k.numel(), k.options()));
+    base += k.numel();
+  }
+  auto stream = cur_stream();
+  while (keys.size() > 1) {
+    std::vector<torch::Tensor> nk, nr;
+    for (size_t j = 0; j + 1 < keys.size(); j += 2) {
+      int64_t nA = keys[j].numel(), nB = keys[j + 1].numel();
+      auto kO = torch::empty({nA + nB}, keys[j].options());
+      auto vO = torch::empty({nA + nB}, keys[j].options());
+      if (nA + nB)  // an empty pair would be a grid of 0 blocks
+        launch_merge_pairs(
+            (const uint64_t*)keys[j].data_ptr(), (const uint64_t*)rows[j].data_ptr(), nA,
+            (const uint64_t*)keys[j + 1].data_ptr(), (const uint64_t*)rows[j + 1].data_ptr(), nB,
+            (uint64_t*)kO.data_ptr(), (uint64_t*)vO.data_ptr(), stream);
+      nk.push_back(kO);
+      nr.push_back(vO);
+    }
+    if (keys.size() % 2) {
+      nk.push_back(keys.back());
+      nr.push_back(rows.back());
+    }
+    keys = std::move(nk);
+    rows = std::move(nr);
+  }
+  return {keys[0], rows[0]};
 }
 
 static torch::Tensor group_start_mask(torch::Tensor keys) {
@@ -257,9 +186,11 @@ static torch::Tensor pack_key_2xi32(torch::Tensor hi, torch::Tensor lo) {
 
 // ---- gathers ----------------------------------------------------------- //
 
-static std::vector<torch::Tensor> gather_fixed_multi(std::vector<torch::Tensor> cols,
-                                                     torch::Tensor idx) {
-  for (auto& c : cols) CHECK_GPU_NONEMPTY(c);
+// out[c][i] = cols[c][idx[i]] for every column, 16 columns per launch (the
+// gather_fixed_multi binding). A column is 1-d of any 1/2/4/8-byte dtype,
+// or [rows, es] whose es-wide rows move as one element.
+static std::vector<torch::Tensor> gather_fixed(std::vector<torch::Tensor> cols,
+                                               torch::Tensor idx) {
   CHECK_GPU(idx);
   int64_t n = idx.numel();
   std::vector<torch::Tensor> outs;
@@ -268,17 +199,46 @@ static std::vector<torch::Tensor> gather_fixed_multi(std::vector<torch::Tensor> 
     GatherTable tbl;
     tbl.ncols = 0;
     for (; c < cols.size() && tbl.ncols < 16; c++) {
-      CHECK_GPU(cols[c]);
-      auto out = torch::empty({n}, cols[c].options());
-      tbl.src[tbl.ncols] = cols[c].data_ptr();
+      auto& col = cols[c];
+      CHECK_GPU(col);
+      bool wide = col.dim() == 2;
+      int64_t es = col.element_size() * (wide ? col.size(1) : 1);
+      TORCH_CHECK(es == 1 || es == 2 || es == 4 || es == 8,
+                  "gather_fixed: unsupported elem size ", es);
+      auto out = wide ? torch::empty({n, col.size(1)}, col.options())
+                      : torch::empty({n}, col.options());
+      tbl.src[tbl.ncols] = col.data_ptr();
       tbl.dst[tbl.ncols] = out.data_ptr();
-      tbl.esize[tbl.ncols] = (int)cols[c].element_size();
+      tbl.esize[tbl.ncols] = (int)es;
       tbl.ncols++;
       outs.push_back(out);
     }
     launch_gather_fixed_multi(tbl, idx.data_ptr<int64_t>(), n, cur_stream());
   }
   return outs;
+}
+
+// Rows idx of a string column -> (new_offsets, new_bytes). One host sync,
+// at the byte total.
+static std::pair<torch::Tensor, torch::Tensor> take_strings(
+    torch::Tensor bytes, torch::Tensor offsets, torch::Tensor idx) {
+  CHECK_GPU_NONEMPTY(bytes);
+  CHECK_GPU(offsets);
+  CHECK_GPU(idx);
+  TORCH_CHECK(offsets.scalar_type() == torch::kInt64 && offsets.numel() >= 1 &&
+                  idx.scalar_type() == torch::kInt64,
+              "take_strings: offsets (rows + 1) and idx must be int64");
+  int64_t n = idx.numel(), nrows = offsets.numel() - 1;
+  auto lens = offsets.narrow(0, 1, nrows) - offsets.narrow(0, 0, nrows);
+  auto new_offs = torch::zeros({n + 1}, offsets.options());
+  new_offs.narrow(0, 1, n).copy_(at::cumsum(lens.index({idx}), 0));
+  int64_t total = n ? new_offs[n].item<int64_t>() : 0;
+  TORCH_CHECK(total == 0 || bytes.numel(), "take_strings: offsets past empty bytes");
+  auto new_bytes = torch::empty({total}, offsets.options().dtype(torch::kUInt8));
+  launch_gather_strings(opt_u8(bytes), offsets.data_ptr<int64_t>(),
+                        idx.data_ptr<int64_t>(), new_offs.data_ptr<int64_t>(),
+                        new_bytes.data_ptr<uint8_t>(), n, cur_stream());
+  return {new_offs, new_bytes};
 }
 
 static torch::Tensor gather_strings(torch::Tensor src_bytes, torch::Tensor src_offsets,
@@ -355,7 +315,10 @@ static torch::Tensor segmented_last(torch::Tensor grp, torch::Tensor contrib,
 
 // ---- ANN scoring (MFMA) ------------------------------------------------ //
 
-static torch::Tensor ann_scores(torch::Tensor X, torch::Tensor Q) {
+// X (n, K) bf16, Q (nq, K) bf16 -> f32 scores, (n, nq) or query-major
+// (nq, n): the per-query top-k then reads contiguous rows (28 ms -> 2.5 ms
+// for 5M x 64 k=10; benchmarks/topk_micro.py)
+static torch::Tensor ann_scores(torch::Tensor X, torch::Tensor Q, bool query_major) {
   CHECK_GPU(X);
   CHECK_GPU(Q);
   TORCH_CHECK(X.scalar_type() == torch::kBFloat16 && Q.scalar_type() == torch::kBFloat16,
@@ -366,31 +329,11 @@ static torch::Tensor ann_scores(torch::Tensor X, torch::Tensor Q) {
   TORCH_CHECK(Q.size(1) == K, "dim mismatch");
   TORCH_CHECK(K % 32 == 0, "K must be a multiple of 32");
   TORCH_CHECK(nq % 16 == 0, "nq must be a multiple of 16 (pad queries)");
-  auto out = torch::empty({n, nq}, X.options().dtype(torch::kFloat32));
-  launch_ann_scores((const short*)X.data_ptr(), (const short*)Q.data_ptr(),
-                    out.data_ptr<float>(), n, (int32_t)nq, (int32_t)K,
-                    cur_stream());
-  return out;
-}
-
-// query-major output (nq, n): the per-query top-k then reads contiguous
-// rows (28 ms -> 2.5 ms for 5M x 64 k=10; benchmarks/topk_micro.py)
-static torch::Tensor ann_scores_t(torch::Tensor X, torch::Tensor Q) {
-  CHECK_GPU(X);
-  CHECK_GPU(Q);
-  TORCH_CHECK(X.scalar_type() == torch::kBFloat16 &&
-                  Q.scalar_type() == torch::kBFloat16,
-              "ann_scores_t expects bf16");
-  int64_t n = X.size(0);
-  int64_t nq = Q.size(0);
-  int64_t K = X.size(1);
-  TORCH_CHECK(Q.size(1) == K, "dim mismatch");
-  TORCH_CHECK(K % 32 == 0, "K must be a multiple of 32");
-  TORCH_CHECK(nq % 16 == 0, "nq must be a multiple of 16 (pad queries)");
-  auto out = torch::empty({nq, n}, X.options().dtype(torch::kFloat32));
-  launch_ann_scores_t((const short*)X.data_ptr(), (const short*)Q.data_ptr(),
-                      out.data_ptr<float>(), n, (int32_t)nq, (int32_t)K,
-                      cur_stream());
+  auto f32 = X.options().dtype(torch::kFloat32);
+  auto out = query_major ? torch::empty({nq, n}, f32) : torch::empty({n, nq}, f32);
+  (query_major ? launch_ann_scores_t : launch_ann_scores)(
+      (const short*)X.data_ptr(), (const short*)Q.data_ptr(),
+      out.data_ptr<float>(), n, (int32_t)nq, (int32_t)K, cur_stream());
   return out;
 }
 
@@ -495,20 +438,10 @@ static py::object tensor_or_none(const torch::Tensor& t) {
   return t.defined() ? py::cast(t) : py::none();
 }
 
-// One entry per unit column (row-major file, col); None for a column the
-// file does not have. fixed width: (bytes_u8, validity_or_None); string
-// and list: (offsets_i64, bytes_u8, validity_or_None) — list offsets
-// count ELEMENTS.
-static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
-                            torch::Tensor dicts, torch::Tensor runs,
-                            torch::Tensor soffs, torch::Tensor desc,
-                            int64_t nfiles, int64_t ncols) {
-  std::vector<UnitCol> cols;
-  {
-    py::gil_scoped_release rel;
-    cols = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
-                            nfiles, ncols);
-  }
+// Unit columns as python entries; None for a column the file does not
+// have. fixed width: (bytes_u8, validity_or_None); string and list:
+// (offsets_i64, bytes_u8, validity_or_None) — list offsets count ELEMENTS.
+static py::list unit_cols_to_py(const std::vector<UnitCol>& cols) {
   py::list out;
   for (auto& c : cols) {
     if (!c.present)
@@ -521,192 +454,134 @@ static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
   return out;
 }
 
-// C++ scan-unit driver (simple path): decode + UseLast merge + gather for
+// One entry per unit column (row-major file, col).
+static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
+                            torch::Tensor dicts, torch::Tensor runs,
+                            torch::Tensor soffs, torch::Tensor desc,
+                            int64_t nfiles, int64_t ncols) {
+  std::vector<UnitCol> cols;
+  {
+    py::gil_scoped_release rel;
+    cols = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
+                            nfiles, ncols);
+  }
+  return unit_cols_to_py(cols);
+}
+
+// Each read column of a decoded unit (no absent or list columns)
+// concatenated across its files in file order: one UnitCol per column.
+// Fixed-width data comes back as [rows, es]. Validity is defined when any
+// file has one; files without are filled with ones. String offsets are
+// rebased onto the concatenated bytes.
+static std::vector<UnitCol> concat_unit_files(const std::vector<UnitCol>& flat,
+                                              const torch::Tensor& desc,
+                                              int64_t nfiles, int64_t ncols) {
+  auto da = desc.accessor<int64_t, 2>();
+  std::vector<UnitCol> out((size_t)ncols);
+  for (int64_t c = 0; c < ncols; c++) {
+    auto part = [&](int64_t f) -> const UnitCol& { return flat[(size_t)(f * ncols + c)]; };
+    auto cat = [&](auto piece) {
+      std::vector<torch::Tensor> parts;
+      for (int64_t f = 0; f < nfiles; f++) parts.push_back(piece(f));
+      return nfiles == 1 ? parts[0] : at::cat(parts, 0);
+    };
+    UnitCol& o = out[(size_t)c];
+    o.present = true;
+    o.is_string = part(0).is_string;
+    torch::Tensor a_valid;  // some file's validity, if any has one
+    for (int64_t f = 0; f < nfiles; f++)
+      if (part(f).validity.defined()) a_valid = part(f).validity;
+    if (a_valid.defined())
+      o.validity = cat([&](int64_t f) {
+        auto& v = part(f).validity;
+        return v.defined() ? v : torch::ones({da[f * ncols + c][UD_NUM_VALUES]}, a_valid.options());
+      });
+    if (!o.is_string) {
+      int64_t es = da[c][UD_ESIZE];
+      o.data = cat([&](int64_t f) { return part(f).data.view({-1, es}); });
+      continue;
+    }
+    int64_t byte_base = 0;
+    o.offsets = cat([&](int64_t f) {
+      auto offs = part(f).offsets;
+      // later files: shift by the bytes before them, drop the leading 0
+      if (f) offs = (offs + byte_base).narrow(0, 1, offs.numel() - 1);
+      byte_base += part(f).bytes.numel();
+      return offs;
+    });
+    o.bytes = cat([&](int64_t f) { return part(f).bytes; });
+  }
+  return out;
+}
+
+// C++ scan-unit driver (simple path): decode + UseLast merge + take for
 // one unit entirely from C++ — the python per-unit op storm (GIL-bound)
 // was the scan's critical path. Covers: integer single-PK (int64/int32),
-// every-column UseLast, no CDC, no lists. Python falls back otherwise.
-// Returns one entry per read col (the merged row count is implicit in the
-// tensor sizes):
-//   fixed: [data_u8_gathered, validity_or_None]
-//   string: [offsets_i64, bytes_u8, validity_or_None]
-static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf,
-                                  torch::Tensor dicts, torch::Tensor runs,
-                                  torch::Tensor soffs, torch::Tensor desc,
-                                  int64_t nfiles, int64_t ncols, int64_t pk_ci,
-                                  int64_t pk_es) {
-  py::gil_scoped_release rel;  // long device-side section (incl. one sync)
-  auto device = vals.device();
-  auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(device);
-  auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(device);
-  auto stream = cur_stream();
-
+// every-column UseLast, no CDC, no lists, no absent columns. Python falls
+// back otherwise. One merged UnitCol per read column. Host syncs: one at
+// nonzero, one per string column at its byte total.
+static std::vector<UnitCol> scan_unit_uselast_cols(
+    const torch::Tensor& vals, const torch::Tensor& validity_buf,
+    const torch::Tensor& dicts, const torch::Tensor& runs,
+    const torch::Tensor& soffs, const torch::Tensor& desc, int64_t nfiles,
+    int64_t ncols, int64_t pk_ci, int64_t pk_es) {
+  TORCH_CHECK(nfiles >= 1 && pk_ci >= 0 && pk_ci < ncols && (pk_es == 4 || pk_es == 8),
+              "scan_unit_uselast: bad pk column");
   auto flat = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
                                nfiles, ncols);
   for (auto& c : flat)
     TORCH_CHECK(c.present && !c.is_list,
                 "scan_unit_uselast: absent or list column (fallback)");
-  auto da = desc.accessor<int64_t, 2>();
-  auto col = [&](int64_t f, int64_t c) -> UnitCol& {
-    return flat[(size_t)(f * ncols + c)];
-  };
 
-  // ---- pack keys per file + pairwise merge-path merges ----
-  std::vector<std::pair<torch::Tensor, torch::Tensor>> streams;
-  int64_t base = 0;
+  // pack and merge the per-file keys
+  std::vector<torch::Tensor> file_keys;
   for (int64_t f = 0; f < nfiles; f++) {
-    int64_t nv = da[f * ncols + pk_ci][UD_NUM_VALUES];
-    auto& pkc = col(f, pk_ci);
-    torch::Tensor key64;
-    if (pk_es == 8) {
-      key64 = pkc.data.view(torch::kInt64);
-    } else {
-      key64 = pkc.data.view(torch::kInt32).to(torch::kInt64);
-    }
-    auto keys = torch::empty({nv}, i64);
-    launch_pack_key_i64(key64.data_ptr<int64_t>(), (uint64_t*)keys.data_ptr(), nv, stream);
-    auto vals_idx = torch::arange(base, base + nv, i64);
-    streams.emplace_back(keys, vals_idx);
-    base += nv;
+    auto& pk = flat[(size_t)(f * ncols + pk_ci)].data;
+    file_keys.push_back(pack_key_i64(
+        pk_es == 8 ? pk.view(torch::kInt64) : pk.view(torch::kInt32).to(torch::kInt64)));
   }
-  while (streams.size() > 1) {
-    std::vector<std::pair<torch::Tensor, torch::Tensor>> nxt;
-    for (size_t j = 0; j + 1 < streams.size(); j += 2) {
-      auto& A = streams[j];
-      auto& B = streams[j + 1];
-      int64_t nA = A.first.numel(), nB = B.first.numel();
-      auto kO = torch::empty({nA + nB}, i64);
-      auto vO = torch::empty({nA + nB}, i64);
-      launch_merge_pairs((const uint64_t*)A.first.data_ptr(), (const uint64_t*)A.second.data_ptr(), nA,
-                         (const uint64_t*)B.first.data_ptr(), (const uint64_t*)B.second.data_ptr(), nB,
-                         (uint64_t*)kO.data_ptr(), (uint64_t*)vO.data_ptr(), stream);
-      nxt.emplace_back(kO, vO);
-    }
-    if (streams.size() % 2) nxt.push_back(streams.back());
-    streams = std::move(nxt);
-  }
-  torch::Tensor keys = streams[0].first;
-  torch::Tensor order = streams[0].second;
+  auto [keys, order] = merge_key_streams(std::move(file_keys));
+
+  // keep-last: source row of each surviving key
   int64_t n = keys.numel();
+  auto keep = torch::empty({n}, keys.options().dtype(torch::kUInt8));
+  launch_keep_last((const uint64_t*)keys.data_ptr(), keep.data_ptr<uint8_t>(), n,
+                   cur_stream());
+  auto src_idx = order.index({at::nonzero(keep).view(-1)});
 
-  // ---- dedup keep-last + survivor source indices ----
-  auto keep = torch::empty({n}, u8);
-  launch_keep_last((const uint64_t*)keys.data_ptr(), keep.data_ptr<uint8_t>(), n, stream);
-  auto surv = at::nonzero(keep).view(-1);  // the unit's single device sync
-  auto src_idx = order.index({surv});
-
-  // ---- gather every column (concat across files first) ----
-  std::vector<torch::Tensor> g_in;
-  std::vector<int64_t> g_col;  // read col index per g_in entry (fixed/validity)
-  std::vector<int> g_kind;     // 0=data, 1=validity
-  for (int64_t c = 0; c < ncols; c++) {
-    bool is_str = col(0, c).is_string;
-    bool any_valid = false;
-    for (int64_t f = 0; f < nfiles; f++)
-      if (col(f, c).validity.defined()) any_valid = true;
-    if (!is_str) {
-      std::vector<torch::Tensor> parts;
-      int64_t es = da[c][UD_ESIZE];
-      for (int64_t f = 0; f < nfiles; f++)
-        parts.push_back(col(f, c).data.view({-1, es}));
-      auto cat = nfiles == 1 ? parts[0] : at::cat(parts, 0);
-      // gather as typed elements (view to es-wide rows then index)
-      g_in.push_back(cat);
-      g_col.push_back(c);
-      g_kind.push_back(0);
-    }
-    if (any_valid || is_str) {
-      std::vector<torch::Tensor> parts;
-      for (int64_t f = 0; f < nfiles; f++) {
-        auto v = col(f, c).validity;
-        if (v.defined()) parts.push_back(v);
-        else parts.push_back(torch::ones({da[f * ncols + c][UD_NUM_VALUES]}, u8));
-      }
-      if (any_valid) {
-        g_in.push_back(nfiles == 1 ? parts[0] : at::cat(parts, 0));
-        g_col.push_back(c);
-        g_kind.push_back(1);
-      }
-    }
+  // concatenate per column, take the survivors (fixed-width data and
+  // validity of every column in fused gathers)
+  auto cols = concat_unit_files(flat, desc, nfiles, ncols);
+  std::vector<torch::Tensor> fixed;
+  for (auto& c : cols) {
+    if (!c.is_string) fixed.push_back(c.data);
+    if (c.validity.defined()) fixed.push_back(c.validity);
   }
-  // fused fixed-width gathers (16 cols per launch)
-  std::vector<torch::Tensor> g_out(g_in.size());
+  auto taken = gather_fixed(std::move(fixed), src_idx);
+  size_t t = 0;
+  for (auto& c : cols) {
+    if (!c.is_string) c.data = taken[t++].view(-1);
+    if (c.validity.defined()) c.validity = taken[t++];
+    if (c.is_string)
+      std::tie(c.offsets, c.bytes) = take_strings(c.bytes, c.offsets, src_idx);
+  }
+  return cols;
+}
+
+// One entry per read column (the merged row count is implicit in the
+// tensor sizes).
+static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf,
+                                  torch::Tensor dicts, torch::Tensor runs,
+                                  torch::Tensor soffs, torch::Tensor desc,
+                                  int64_t nfiles, int64_t ncols, int64_t pk_ci,
+                                  int64_t pk_es) {
+  std::vector<UnitCol> cols;
   {
-    size_t i = 0;
-    int64_t nsurv = src_idx.numel();
-    while (i < g_in.size()) {
-      GatherTable tbl;
-      tbl.ncols = 0;
-      for (; i < g_in.size() && tbl.ncols < 16; i++) {
-        auto& t = g_in[i];
-        int64_t es = t.dim() == 2 ? t.size(1) * t.element_size() : t.element_size();
-        auto o = torch::empty({nsurv, t.dim() == 2 ? t.size(1) : 1},
-                              t.options());
-        tbl.src[tbl.ncols] = t.data_ptr();
-        tbl.dst[tbl.ncols] = o.data_ptr();
-        tbl.esize[tbl.ncols] = (int)es;
-        tbl.ncols++;
-        g_out[i] = o;
-      }
-      launch_gather_fixed_multi(tbl, src_idx.data_ptr<int64_t>(), nsurv, stream);
-    }
+    py::gil_scoped_release rel;  // long device-side section
+    cols = scan_unit_uselast_cols(vals, validity_buf, dicts, runs, soffs, desc,
+                                  nfiles, ncols, pk_ci, pk_es);
   }
-  // build outputs per column
-  std::vector<torch::Tensor> col_data((size_t)ncols), col_valid((size_t)ncols);
-  std::vector<std::vector<torch::Tensor>> out_cols;
-  for (size_t i = 0; i < g_in.size(); i++) {
-    if (g_kind[i] == 0) col_data[(size_t)g_col[i]] = g_out[i].view(-1);
-    else col_valid[(size_t)g_col[i]] = g_out[i].view(-1);
-  }
-  for (int64_t c = 0; c < ncols; c++) {
-    std::vector<torch::Tensor> entry;
-    if (!col(0, c).is_string) {
-      entry.push_back(col_data[(size_t)c]);
-      entry.push_back(col_valid[(size_t)c]);  // may be undefined
-    } else {
-      // string gather: offsets via cumsum of gathered lens, bytes kernel
-      std::vector<torch::Tensor> offs_parts, bytes_parts;
-      int64_t byte_base = 0;
-      std::vector<torch::Tensor> adj_offs;
-      for (int64_t f = 0; f < nfiles; f++) {
-        auto o = col(f, c).offsets;
-        adj_offs.push_back((f == 0 ? o : o + byte_base));
-        bytes_parts.push_back(col(f, c).bytes);
-        byte_base += col(f, c).bytes.numel();
-      }
-      // concatenated offsets: drop leading 0 of subsequent files
-      std::vector<torch::Tensor> oparts;
-      for (int64_t f = 0; f < nfiles; f++)
-        oparts.push_back(f == 0 ? adj_offs[f] : adj_offs[f].narrow(0, 1, adj_offs[f].numel() - 1));
-      auto cat_offs = nfiles == 1 ? oparts[0] : at::cat(oparts, 0);
-      auto cat_bytes = nfiles == 1 ? bytes_parts[0] : at::cat(bytes_parts, 0);
-      auto lens = cat_offs.narrow(0, 1, cat_offs.numel() - 1) -
-                  cat_offs.narrow(0, 0, cat_offs.numel() - 1);
-      auto sel_lens = lens.index({src_idx});
-      int64_t nsurv = src_idx.numel();
-      auto new_offs = torch::zeros({nsurv + 1}, i64);
-      new_offs.narrow(0, 1, nsurv).copy_(at::cumsum(sel_lens, 0));
-      int64_t total = nsurv ? new_offs[nsurv].item<int64_t>() : 0;
-      auto new_bytes = torch::empty({total}, u8);
-      launch_gather_strings(cat_bytes.data_ptr<uint8_t>(), cat_offs.data_ptr<int64_t>(),
-                            src_idx.data_ptr<int64_t>(), new_offs.data_ptr<int64_t>(),
-                            new_bytes.data_ptr<uint8_t>(), nsurv, stream);
-      entry.push_back(new_offs);
-      entry.push_back(new_bytes);
-      entry.push_back(col_valid[(size_t)c]);  // may be undefined
-    }
-    out_cols.push_back(std::move(entry));
-  }
-  py::gil_scoped_acquire acq;
-  py::list out_list;
-  for (auto& entry : out_cols) {
-    py::list e;
-    for (auto& t : entry) {
-      if (t.defined()) e.append(t);
-      else e.append(py::none());
-    }
-    out_list.append(e);
-  }
-  return out_list;
+  return unit_cols_to_py(cols);
 }
 
 // decompress into an existing device buffer (jobs dst offsets index it)
@@ -746,8 +621,8 @@ static torch::Tensor zstd_decompress_into(torch::Tensor src, torch::Tensor jobs,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("ann_scores", &ann_scores);
-  m.def("ann_scores_t", &ann_scores_t);
+  m.def("ann_scores", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, false); });
+  m.def("ann_scores_t", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, true); });
   m.def("zstd_decompress_into", &zstd_decompress_into);
   m.def("str_chunk_keys", [](torch::Tensor offsets, torch::Tensor bytes,
                              int64_t chunk) {
@@ -771,39 +646,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     launch_hamming_scores((const uint64_t*)codes.data_ptr<int64_t>(),
                           (const uint64_t*)qcodes.data_ptr<int64_t>(),
                           out.data_ptr<int32_t>(), n, nq, words, cur_stream());
-    return out;
-  });
-  m.def("fastscan_bit_dot", [](torch::Tensor bits, torch::Tensor q,
-                               int64_t dim) {
-    // bits (m, w) uint8 cuda; q (nq, dim) f32 cuda -> (m, nq) f32 of
-    // <sign_bits, q> (RaBitQ stage-1 FastScan, LDS-LUT kernel)
-    CHECK_GPU(bits);
-    CHECK_GPU(q);
-    TORCH_CHECK(bits.dtype() == torch::kUInt8 && bits.is_contiguous());
-    TORCH_CHECK(q.dtype() == torch::kFloat32);
-    int64_t m = bits.size(0);
-    int w = (int)bits.size(1);
-    int nq = (int)q.size(0);
-    int g = (int)((dim + 3) / 4);
-    TORCH_CHECK(w == (dim + 7) / 8, "bits width mismatch");
-    // per-query LUT: (nq, g, 16); entry v = sum_j q[4g+j]*((v>>j)&1)
-    auto qp = torch::zeros({nq, (int64_t)g * 4}, q.options());
-    qp.slice(1, 0, dim).copy_(q);
-    auto qg = qp.view({nq, g, 4});
-    static float pat_host[16 * 4];
-    static bool pat_init = false;
-    if (!pat_init) {
-      for (int v = 0; v < 16; v++)
-        for (int j = 0; j < 4; j++) pat_host[v * 4 + j] = (float)((v >> j) & 1);
-      pat_init = true;
-    }
-    auto pat = torch::from_blob(pat_host, {16, 4},
-                                torch::TensorOptions().dtype(torch::kFloat32))
-                   .to(q.device());
-    auto lut = torch::matmul(qg, pat.t()).contiguous();  // (nq, g, 16)
-    auto out = torch::empty({m, nq}, q.options());
-    launch_fastscan_lut(bits.data_ptr<uint8_t>(), lut.data_ptr<float>(),
-                        out.data_ptr<float>(), m, nq, w, g, cur_stream());
     return out;
   });
   m.def("fastscan_est", [](torch::Tensor bits, torch::Tensor q, int64_t dim,
@@ -832,14 +674,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto qp = torch::zeros({nq, (int64_t)g * 4}, q.options());
     qp.slice(1, 0, dim).copy_(q);
     auto qg = qp.view({nq, g, 4});
-    static float pat_host2[16 * 4];
-    static bool pat_init2 = false;
-    if (!pat_init2) {
+    static float pat_host[16 * 4];
+    static bool pat_init = false;
+    if (!pat_init) {
       for (int v = 0; v < 16; v++)
-        for (int j = 0; j < 4; j++) pat_host2[v * 4 + j] = (float)((v >> j) & 1);
-      pat_init2 = true;
+        for (int j = 0; j < 4; j++) pat_host[v * 4 + j] = (float)((v >> j) & 1);
+      pat_init = true;
     }
-    auto pat = torch::from_blob(pat_host2, {16, 4},
+    auto pat = torch::from_blob(pat_host, {16, 4},
                                 torch::TensorOptions().dtype(torch::kFloat32))
                    .to(q.device());
     auto lut = torch::matmul(qg, pat.t()).contiguous();
@@ -852,23 +694,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         g_add.contiguous().data_ptr<float>(),
         c1_sum_q.contiguous().data_ptr<float>(), out.data_ptr<float>(), m, nq,
         w, g, kc, cur_stream());
-    return out;
-  });
-  m.def("fastscan_ex_dot", [](torch::Tensor ex, torch::Tensor q, int64_t dim) {
-    // ex (m, wn) uint8 nibbles cuda; q (nq, dim) f32 -> (m, nq) f32
-    CHECK_GPU(ex);
-    CHECK_GPU(q);
-    TORCH_CHECK(ex.dtype() == torch::kUInt8 && ex.is_contiguous());
-    TORCH_CHECK(q.dtype() == torch::kFloat32);
-    int64_t m = ex.size(0);
-    int wn = (int)ex.size(1);
-    int nq = (int)q.size(0);
-    TORCH_CHECK(wn == (dim + 1) / 2, "ex width mismatch");
-    auto qc = q.contiguous();
-    auto out = torch::empty({m, nq}, q.options());
-    launch_fastscan_ex_dot(ex.data_ptr<uint8_t>(), qc.data_ptr<float>(),
-                           out.data_ptr<float>(), m, nq, wn, (int)dim,
-                           cur_stream());
     return out;
   });
   m.def("fastscan_ex_dot_pairs",
@@ -904,15 +729,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hash_fixed_column", &hash_fixed_column);
   m.def("hash_string_column", &hash_string_column);
   m.def("bucket_ids", &bucket_ids);
-  m.def("rle_expand", &rle_expand);
-  m.def("dict_gather_scatter", &dict_gather_scatter);
-  m.def("scatter_valid", &scatter_valid);
-  m.def("merge_pairs", &merge_pairs);
-  m.def("keep_last_mask", &keep_last_mask);
+  m.def("merge_sorted_keys", &merge_key_streams);
   m.def("group_start_mask", &group_start_mask);
   m.def("pack_key_i64", &pack_key_i64);
   m.def("pack_key_2xi32", &pack_key_2xi32);
-  m.def("gather_fixed_multi", &gather_fixed_multi);
+  m.def("gather_fixed_multi", &gather_fixed);
+  m.def("take_strings", &take_strings);
   m.def("gather_strings", &gather_strings);
   m.def("bytes_ne_mask", &bytes_ne_mask);
   m.def("segmented_sum", &segmented_sum);

@@ -1,0 +1,105 @@
+// Host-side interface of the gfx950 kernels: every launcher the torch
+// bindings (hip_module.cc) call, declared once and included by the .hip
+// file that defines it: a definition that drifts from its declaration
+// leaves an undefined symbol, and the extension fails to import.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace lakesoul {
+
+// kernels.hip — hashing
+void launch_hash_fixed(int dt, const void* data, const uint8_t* validity,
+                       const int64_t* prev, int64_t* out, int64_t n, int first,
+                       hipStream_t s);
+void launch_hash_string(const int32_t* offsets, const uint8_t* bytes,
+                        const uint8_t* validity, const int64_t* prev,
+                        int64_t* out, int64_t n, int first, hipStream_t s);
+void launch_bucket_ids(const int64_t* hashes, int32_t* out, int64_t n,
+                       uint32_t nb, hipStream_t s);
+
+// kernels.hip — decode
+void launch_rle_expand(const uint8_t* payload, const int64_t* runs,
+                       int64_t nruns, int32_t* out, int64_t n, hipStream_t s);
+template <typename T>
+void launch_dict_gather_scatter(const T* dict, const int32_t* idx,
+                                const uint8_t* validity, const int64_t* pos,
+                                T* out, int64_t n, hipStream_t s);
+template <typename T>
+void launch_scatter_valid(const T* dense, const uint8_t* validity,
+                          const int64_t* pos, T* out, int64_t n, hipStream_t s);
+
+// kernels.hip — merge
+void launch_merge_pairs(const uint64_t* kA, const uint64_t* vA, int64_t nA,
+                        const uint64_t* kB, const uint64_t* vB, int64_t nB,
+                        uint64_t* kOut, uint64_t* vOut, hipStream_t s);
+void launch_keep_last(const uint64_t* keys, uint8_t* keep, int64_t n, hipStream_t s);
+void launch_group_start(const uint64_t* keys, uint8_t* start, int64_t n, hipStream_t s);
+void launch_pack_key_i64(const int64_t* x, uint64_t* out, int64_t n, hipStream_t s);
+void launch_pack_key_2xi32(const int32_t* hi, const int32_t* lo, uint64_t* out,
+                           int64_t n, hipStream_t s);
+
+// kernels.hip — gathers. GatherTable is passed BY VALUE into
+// gather_fixed_multi_kernel: this is its only definition.
+struct GatherTable {
+  const void* src[16];
+  void* dst[16];
+  int esize[16];
+  int ncols;
+};
+void launch_gather_fixed_multi(const GatherTable& tbl, const int64_t* idx,
+                               int64_t n, hipStream_t s);
+void launch_gather_strings(const uint8_t* src_bytes, const int64_t* src_off,
+                           const int64_t* idx, const int64_t* dst_off,
+                           uint8_t* dst_bytes, int64_t n, hipStream_t s);
+void launch_bytes_ne_mask(const int64_t* offsets, const uint8_t* bytes,
+                          const uint8_t* pattern, int plen, uint8_t* out,
+                          int64_t n, hipStream_t s);
+
+// kernels.hip — segmented merge operators
+template <typename T, typename ACC>
+void launch_segmented_sum(const T* vals, const int64_t* grp, const uint8_t* contrib,
+                          const uint8_t* validity, ACC* out_sum,
+                          int32_t* out_has_null, int64_t n, hipStream_t s);
+void launch_segmented_last(const int64_t* grp, const uint8_t* contrib,
+                           const uint8_t* validity, int64_t* out_idx, int64_t n,
+                           hipStream_t s);
+
+// kernels.hip — string-PK sort keys, binary-code scorer
+void launch_str_chunk_keys(const int64_t* offsets, const uint8_t* bytes,
+                           int64_t chunk, int64_t* out, int64_t n,
+                           hipStream_t s);
+void launch_hamming_scores(const uint64_t* codes, const uint64_t* qcodes,
+                           int32_t* out, int64_t n, int nq, int words,
+                           hipStream_t s);
+
+// ann.hip
+void launch_ann_scores(const short* X, const short* Q, float* out, int64_t n,
+                       int32_t nq, int32_t K, hipStream_t s);
+void launch_ann_scores_t(const short* X, const short* Q, float* out, int64_t n,
+                         int32_t nq, int32_t K, hipStream_t s);
+
+// fastscan.hip
+void launch_fastscan_est(const uint8_t* bits, const float* lut,
+                         const float* f_add, const float* f_rescale,
+                         const int32_t* cl_of_row, const float* g_add,
+                         const float* c1_sum_q, float* out, int64_t m,
+                         int32_t nq, int32_t w, int32_t g,
+                         int32_t n_clusters, hipStream_t s);
+void launch_fastscan_ex_dot_pairs(const uint8_t* ex, const int64_t* cand,
+                                  const float* qv, float* out, int32_t C,
+                                  int32_t nq, int32_t wn, int32_t dim,
+                                  hipStream_t s);
+
+// snappy.hip, zstd.hip
+void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
+                              int64_t njobs, uint8_t* dst, int32_t* status,
+                              hipStream_t s);
+void launch_zstd_decompress(const uint8_t* src, const int64_t* jobs,
+                            int64_t njobs, uint8_t* dst, uint8_t* scratch,
+                            int64_t nblocks, int32_t* status, hipStream_t s);
+int64_t lsz_gpu_litbuf_bytes();
+
+}  // namespace lakesoul

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "../cpp/murmur3.h"
+#include "kernels.h"
 
 namespace lakesoul {
 
@@ -293,14 +294,8 @@ __global__ void pack_key_2xi32_kernel(const int32_t* __restrict__ hi,
 // ===================================================================== //
 
 // fused multi-column fixed-width gather: up to 16 columns per launch.
-// srcs/dsts are device pointer tables; elem sizes per column.
-struct GatherTable {
-  const void* src[16];
-  void* dst[16];
-  int esize[16];
-  int ncols;
-};
-
+// srcs/dsts are device pointer tables; elem sizes per column
+// (struct GatherTable, kernels.h).
 __global__ void gather_fixed_multi_kernel(GatherTable tbl,
                                           const int64_t* __restrict__ idx,
                                           int64_t n) {

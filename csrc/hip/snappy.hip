@@ -15,6 +15,8 @@
 
 #include <cstdint>
 
+#include "kernels.h"
+
 namespace lakesoul {
 
 // jobs: int64 [n][4] = {src_off, src_len, dst_off, dst_len}

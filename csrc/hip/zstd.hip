@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../cpp/zstd_dec.h"
+#include "kernels.h"
 
 namespace lsz_gpu {
 

@@ -201,26 +201,26 @@ class Column:
                           validity=got.validity)
         if self.is_string:
             offs = self.offsets
+            v = None if self.validity is None else self.validity[idx]
+            if offs.device.type != "cpu":
+                from ..ops import hip
+
+                new_offs, nb = hip().take_strings(
+                    self.bytes_, offs.to(torch.int64), idx.to(torch.int64))
+                return Column(self.dtype, None, new_offs.to(offs.dtype), nb, v)
             lens = offs[1:] - offs[:-1]
             new_lens = lens[idx]
             new_offs = torch.zeros(idx.numel() + 1, dtype=offs.dtype, device=offs.device)
             torch.cumsum(new_lens, 0, out=new_offs[1:].view(-1))
-            # gather bytes (CPU loop-free path via numpy for now)
-            if offs.device.type == "cpu":
-                src_off = offs.numpy()
-                src_b = self.bytes_.numpy()
-                sel = idx.numpy()
-                out = np.empty(int(new_offs[-1]), dtype=np.uint8)
-                no = new_offs.numpy()
-                for i, si in enumerate(sel):
-                    out[no[i]:no[i + 1]] = src_b[src_off[si]:src_off[si + 1]]
-                nb = torch.from_numpy(out)
-            else:
-                from ..ops import hip
-
-                nb = hip().gather_strings(self.bytes_, self.offsets.to(torch.int64), idx.to(torch.int64), new_offs.to(torch.int64))
-            v = None if self.validity is None else self.validity[idx]
-            return Column(self.dtype, None, new_offs, nb, v)
+            # gather bytes (numpy loop)
+            src_off = offs.numpy()
+            src_b = self.bytes_.numpy()
+            sel = idx.numpy()
+            out = np.empty(int(new_offs[-1]), dtype=np.uint8)
+            no = new_offs.numpy()
+            for i, si in enumerate(sel):
+                out[no[i]:no[i + 1]] = src_b[src_off[si]:src_off[si + 1]]
+            return Column(self.dtype, None, new_offs, torch.from_numpy(out), v)
         v = None if self.validity is None else self.validity[idx]
         return Column(self.dtype, self.data[idx], None, None, v)
 

@@ -4,8 +4,9 @@ Mirrors merge_cpu.py semantics exactly (same contract as the reference's
 SortedStreamMerger + merge operators); GPU tests compare the two.
 
 Fast path: integer PKs that pack into a u64 order-preserving key use the
-hand-written merge-path kernel (csrc/hip/kernels.hip merge_pairs_kernel)
-to exploit per-file sortedness — K files merge in ceil(log2 K) passes.
+hand-written merge-path kernel (csrc/hip/kernels.hip merge_pairs_kernel,
+driven by _hip.merge_sorted_keys) to exploit per-file sortedness — K
+files merge in ceil(log2 K) passes.
 Generic path: iterated stable argsort (lexsort) on the concatenated keys.
 Dedup (UseLast), segmented sums, last-non-null and CDC filtering run as
 HIP kernels; payload columns are materialized with one fused multi-column
@@ -93,35 +94,15 @@ def merge_key_order(
     back for free (boundary detection reuses it, no re-gather). For other
     PKs (incl. strings) eq_tensors (concat space, most-significant-first)
     drive both the stable LSD sort and group-boundary detection."""
-    offsets = [0]
-    for c in counts:
-        offsets.append(offsets[-1] + c)
-    total = offsets[-1]
-
     per_file_keys = [_pack_keys_one_file(cols) for cols in file_pk_cols]
     if all(k is not None for k in per_file_keys) and len(per_file_keys) >= 1:
-        # merge-path pairwise merge: values carry global row index
-        streams = []
-        for i, k in enumerate(per_file_keys):
-            vals = torch.arange(
-                offsets[i], offsets[i + 1], dtype=torch.int64, device=device
-            )
-            streams.append((k, vals))
-        while len(streams) > 1:
-            nxt = []
-            for j in range(0, len(streams) - 1, 2):
-                kA, vA = streams[j]
-                kB, vB = streams[j + 1]
-                kO, vO = hip().merge_pairs(kA, vA, kB, vB)
-                nxt.append((kO, vO))
-            if len(streams) % 2:
-                nxt.append(streams[-1])
-            streams = nxt
-        return streams[0][1], streams[0][0], None
+        # merge-path pairwise merge: order carries the global row index
+        keys, order = hip().merge_sorted_keys(per_file_keys)
+        return order, keys, None
 
     # generic stable LSD sort on concatenated keys (ties keep concat
     # order = snapshot order, the MOR tie rule)
-    perm = torch.arange(total, dtype=torch.int64, device=device)
+    perm = torch.arange(sum(counts), dtype=torch.int64, device=device)
     sort_tensors: List[torch.Tensor] = []   # most-significant first
     npk = len(file_pk_cols[0])
     for ci in range(npk):
@@ -217,7 +198,7 @@ def merge_sorted_files_gpu(
         # UseLast for every column: survivors = last sorted row per group
         surv_sorted_idx = torch.nonzero(end_mask, as_tuple=True)[0]
         src_idx = order[surv_sorted_idx]
-        out_cols = _gather_all(schema, names, cat_col, src_idx)
+        out_cols = _gather_all(names, cat_col, src_idx)
     else:
         # per-column ops over group structure
         for name in names:
@@ -249,31 +230,28 @@ def merge_sorted_files_gpu(
     return out
 
 
-def _gather_all(schema, names, cat_col, src_idx) -> Dict[str, Column]:
-    out: Dict[str, Column] = {}
-    fixed_names, fixed_tensors = [], []
-    validity_names, validity_tensors = [], []
+def _gather_all(names, cat_col, src_idx) -> Dict[str, Column]:
+    """Rows src_idx of every named column: fixed-width data and validity
+    in fused multi-column gathers, strings through Column.take."""
+    keys, tensors = [], []
     for name in names:
         c = cat_col(name)
-        if not c.is_string:
-            fixed_names.append(name)
-            fixed_tensors.append(c.data)
+        if c.is_string:
+            continue
+        keys.append((name, "data"))
+        tensors.append(c.data)
         if c.validity is not None:
-            validity_names.append(name)
-            validity_tensors.append(c.validity)
-    gathered = hip().gather_fixed_multi(fixed_tensors + validity_tensors, src_idx) if (
-        fixed_tensors or validity_tensors
-    ) else []
-    gmap = dict(zip(fixed_names + ["\0v" + n for n in validity_names], gathered))
+            keys.append((name, "validity"))
+            tensors.append(c.validity)
+    gathered = dict(zip(keys, hip().gather_fixed_multi(tensors, src_idx))) if tensors else {}
+    out: Dict[str, Column] = {}
     for name in names:
         c = cat_col(name)
-        v = gmap.get("\0v" + name)
         if c.is_string:
             out[name] = c.take(src_idx)
-            if v is not None:
-                out[name].validity = v
         else:
-            out[name] = Column(c.dtype, data=gmap[name], validity=v)
+            out[name] = Column(c.dtype, data=gathered[name, "data"],
+                               validity=gathered.get((name, "validity")))
     return out
 
 
@@ -397,10 +375,4 @@ def _apply_op_gpu(f, col: Column, op: str, order, grp, ngroups, seq_sorted,
 
 
 def _gather_one(f, col: Column, src_idx) -> Column:
-    if col.is_string:
-        return col.take(src_idx)
-    outs = hip().gather_fixed_multi(
-        [col.data] + ([col.validity] if col.validity is not None else []), src_idx
-    )
-    return Column(f.dtype, data=outs[0],
-                  validity=outs[1] if col.validity is not None else None)
+    return _gather_all([f.name], lambda _name: col, src_idx)[f.name]

@@ -69,6 +69,9 @@ def test_murmur3_string_and_chaining_gpu(dev):
 
 
 def test_merge_pairs_kernel(dev):
+    """Two sorted streams through merge_sorted_keys (one merge_pairs
+    launch): keys sorted, ties with the older stream first, content equal
+    to the stable sort."""
     from lakesoul_amd.ops import hip
 
     rng = np.random.default_rng(1)
@@ -76,19 +79,38 @@ def test_merge_pairs_kernel(dev):
     b = np.sort(rng.integers(0, 10**6, 37777).astype(np.uint64))
     kA = torch.from_numpy(a.view(np.int64)).to(dev)
     kB = torch.from_numpy(b.view(np.int64)).to(dev)
-    vA = torch.arange(len(a), dtype=torch.int64, device=dev)
-    vB = torch.arange(1_000_000, 1_000_000 + len(b), dtype=torch.int64, device=dev)
-    kO, vO = hip().merge_pairs(kA, vA, kB, vB)
+    kO, vO = hip().merge_sorted_keys([kA, kB])
     keys = kO.cpu().numpy().view(np.uint64)
     assert np.all(keys[1:] >= keys[:-1])
-    # stability: for equal keys A values (< 1e6) come before B values
+    # stability: for equal keys A rows (< len(a)) come before B rows
     vals = vO.cpu().numpy()
     eq = keys[1:] == keys[:-1]
-    bad = eq & (vals[:-1] >= 1_000_000) & (vals[1:] < 1_000_000)
+    bad = eq & (vals[:-1] >= len(a)) & (vals[1:] < len(a))
     assert not bad.any()
     # content preserved
     ref = np.sort(np.concatenate([a, b]), kind="stable")
     np.testing.assert_array_equal(keys, ref)
+
+
+@pytest.mark.parametrize(
+    "lens",
+    [[5], [2047, 2049], [0, 300], [300, 0], [0, 0], [1, 4100, 7],
+     [100, 2048, 1, 0, 3000]],
+    ids=lambda lens: "-".join(map(str, lens)))
+def test_merge_sorted_keys_matches_stable_sort(dev, lens):
+    """K sorted streams with many cross-stream ties: order is exactly the
+    stable argsort of the concatenation (2048 = merge tile; 3 and 5
+    streams carry an odd stream; [0, 0] launches nothing)."""
+    from lakesoul_amd.ops import hip
+
+    rng = np.random.default_rng(sum(lens) + len(lens))
+    streams = [np.sort(rng.integers(0, 51, n)).astype(np.int64) for n in lens]
+    keys, order = hip().merge_sorted_keys(
+        [torch.from_numpy(s).to(dev) for s in streams])
+    concat = np.concatenate(streams)
+    expect = np.argsort(concat, kind="stable")
+    np.testing.assert_array_equal(order.cpu().numpy(), expect)
+    np.testing.assert_array_equal(keys.cpu().numpy(), concat[expect])
 
 
 @pytest.mark.parametrize("stored", ["int64", "int32", "float64"])
@@ -160,6 +182,45 @@ def test_gather_strings_kernel(dev):
     sel = idx.cpu().numpy()
     for i in range(300):
         assert ob[no[i]:no[i + 1]].decode() == strings[sel[i]]
+
+
+def test_take_strings(dev):
+    """take_strings (lengths, cumsum, byte gather in one call) vs a python
+    loop: repeats, an empty index, a single row; Column.take keeps the
+    column's own offsets dtype."""
+    from lakesoul_amd.io.batch import Column
+    from lakesoul_amd.ops import hip
+
+    rng = np.random.default_rng(4)
+    classes = [0, 1, 63, 64, 65, 200]
+    lens = np.concatenate([classes, rng.choice(classes, 194)])
+    rows = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in lens]
+    offs = np.zeros(201, dtype=np.int64)
+    offs[1:] = np.cumsum(lens)
+    by = torch.from_numpy(np.frombuffer(b"".join(rows), dtype=np.uint8).copy()).to(dev)
+    offs_t = torch.from_numpy(offs).to(dev)
+
+    def check(got_offs, got_bytes, rows, sel):
+        want = [rows[i] for i in sel]
+        want_offs = np.zeros(len(sel) + 1, dtype=np.int64)
+        want_offs[1:] = np.cumsum([len(w) for w in want])
+        np.testing.assert_array_equal(got_offs.cpu().numpy(), want_offs)
+        assert got_bytes.cpu().numpy().tobytes() == b"".join(want)
+
+    repeats = np.concatenate([rng.integers(0, 200, 500), np.arange(6), np.arange(6)])
+    for sel in (repeats, np.empty(0, dtype=np.int64), np.array([137])):
+        idx = torch.from_numpy(sel.astype(np.int64)).to(dev)
+        check(*hip().take_strings(by, offs_t, idx), rows, sel)
+    # a column of one row
+    one = torch.from_numpy(np.frombuffer(rows[5], dtype=np.uint8).copy()).to(dev)
+    one_offs = torch.tensor([0, len(rows[5])], dtype=torch.int64, device=dev)
+    idx = torch.zeros(3, dtype=torch.int64, device=dev)
+    check(*hip().take_strings(one, one_offs, idx), [rows[5]], [0, 0, 0])
+
+    col = Column("string", offsets=offs_t.to(torch.int32), bytes_=by)
+    got = col.take(torch.from_numpy(repeats))  # CPU index: moved to the device
+    assert got.offsets.dtype == torch.int32
+    check(got.offsets, got.bytes_, rows, repeats)
 
 
 def _mk_catalog(tmp_path):

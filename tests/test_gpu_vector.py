@@ -110,22 +110,6 @@ def test_gpu_binary_index_recall(dev, tmp_path):
     assert (ids_b[:, 0] == qids).mean() >= 0.95
 
 
-def test_fastscan_bit_dot_vs_oracle(dev):
-    """LDS-LUT 1-bit dot kernel vs the torch unpack oracle
-    (rabitq.py estimate path)."""
-    from lakesoul_amd.ops import hip
-    from lakesoul_amd.vector.rabitq import pack_bits, unpack_bits
-
-    rng = np.random.default_rng(7)
-    for m, nq, dim in [(1000, 4, 64), (4097, 7, 768), (333, 1, 100)]:
-        bits = torch.from_numpy(rng.integers(0, 2, (m, dim)).astype(np.uint8))
-        packed = pack_bits(bits.bool()).to(dev)
-        q = torch.from_numpy(rng.normal(size=(nq, dim)).astype(np.float32)).to(dev)
-        got = hip().fastscan_bit_dot(packed, q, dim).cpu()
-        ref = (bits.to(torch.float32) @ q.cpu().T)
-        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-3)
-
-
 def test_fastscan_est_fused_vs_oracle(dev):
     """Fused estimator kernel vs the torch composition of the same
     quantities."""
@@ -150,20 +134,6 @@ def test_fastscan_est_fused_vs_oracle(dev):
     # f16 LDS LUTs in the query-blocked kernel: ~5e-4 relative per LUT
     # entry — far under the estimate's own 1-bit quantization error
     torch.testing.assert_close(got, ref, rtol=5e-3, atol=5e-2)
-
-
-def test_fastscan_ex_dot_vs_oracle(dev):
-    from lakesoul_amd.ops import hip
-    from lakesoul_amd.vector.rabitq import pack_nibbles, unpack_nibbles
-
-    rng = np.random.default_rng(8)
-    for m, nq, dim in [(500, 3, 64), (2049, 5, 768), (100, 2, 99)]:
-        codes = torch.from_numpy(rng.integers(0, 8, (m, dim)).astype(np.uint8))
-        packed = pack_nibbles(codes).to(dev)
-        q = torch.from_numpy(rng.normal(size=(nq, dim)).astype(np.float32)).to(dev)
-        got = hip().fastscan_ex_dot(packed, q, dim).cpu()
-        ref = codes.to(torch.float32) @ q.cpu().T
-        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-3)
 
 
 def test_fastscan_ex_dot_pairs_vs_oracle(dev):
