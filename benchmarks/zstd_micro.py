@@ -1,5 +1,11 @@
-import numpy as np, torch, time, os, sys
-sys.path.insert(0, "/root/repo")
+"""GPU zstd kernel micro-benchmark: 4096 copies of one 32 KB page per page
+kind, level-1 frames, decoded by one launch of zstd_decompress_into.
+Prints one JSON line per page kind."""
+import json, os, sys, time
+
+import numpy as np, torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lakesoul_amd.ops import cpp, hip
 
 rng = np.random.default_rng(0)
@@ -25,5 +31,7 @@ for name, payload in kinds.items():
         hip().zstd_decompress_into(src, jobs, dst)
     torch.cuda.synchronize()
     dt = (time.time() - t0) / 3
-    gbps = PAGE * npages / dt / 1e9
-    print(f"{name}: ratio {len(payload)/len(comp):.2f}  {dt*1e3:7.2f} ms  {gbps:6.1f} GB/s  blocks={os.environ.get('LAKESOUL_ZSTD_BLOCKS','2048')}")
+    print(json.dumps({
+        "kind": name, "ratio": round(len(payload) / len(comp), 2),
+        "ms": round(dt * 1e3, 3), "gbps": round(PAGE * npages / dt / 1e9, 2),
+        "blocks": int(os.environ.get("LAKESOUL_ZSTD_BLOCKS", "2048"))}), flush=True)

@@ -904,6 +904,54 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     if (n < 0) throw std::runtime_error("lszstd decode failed");
     return py::bytes((const char*)out.data(), (size_t)n);
   });
+  m.def("zstd_frame_census", [](py::bytes bytes) {
+    // what format features the frames in `bytes` use: walks them with the
+    // decoder's parse functions only, decodes nothing
+    using namespace lszstd;
+    std::string buf = bytes;
+    const uint8_t* src = (const uint8_t*)buf.data();
+    const int64_t n = (int64_t)buf.size();
+    std::map<std::string, int64_t> count;
+    auto fail = [] { throw std::runtime_error("zstd_frame_census: bad frame"); };
+    static const char* const kBlock[] = {"raw", "rle", "compressed"};
+    static const char* const kLit[] = {"raw", "rle", "compressed", "treeless"};
+    static const char* const kTable[] = {"ll", "of", "ml"};
+    int64_t ip = 0;
+    while (ip + 4 <= n) {
+      bool skippable, checksum;
+      ip = parse_frame_header(src, n, ip, skippable, checksum);
+      if (ip < 0) fail();
+      if (skippable) continue;
+      BlockHdr b;
+      do {
+        if (!parse_block_header(src + ip, n - ip, b)) fail();
+        ip += 3;
+        count[std::string("block_") + kBlock[b.type]]++;
+        if (b.type == kBlockCompressed) {
+          const uint8_t* p = src + ip;
+          LitHdr h;
+          if (!parse_literals_header(p, b.size, h)) fail();
+          // header form: its length for raw / RLE, the size format otherwise
+          int form = h.type <= kLitRle ? (int)h.hdr : h.sizeFormat;
+          count[std::string("lit_") + kLit[h.type] + "_" + std::to_string(form)]++;
+          if (h.type == kLitCompressed && h.cs >= 1)
+            count[huf_desc_direct(p[h.hdr]) ? "huf_direct" : "huf_fse"]++;
+          p += h.hdr + h.cs;
+          int64_t rem = b.size - (h.hdr + h.cs), nSeq;
+          int used = read_seq_count(p, rem, nSeq);
+          if (used < 0 || (nSeq > 0 && rem < used + 1)) fail();
+          count["nseq_" + std::to_string(used) + "byte"]++;
+          if (nSeq == 0) count["nseq_zero"]++;
+          for (int kind = kSeqLL; nSeq > 0 && kind <= kSeqML; kind++)
+            count[std::string(kTable[kind]) + "_mode_" +
+                  std::to_string(seq_mode(p[used], kind))]++;
+        }
+        ip += b.srcBytes;
+      } while (!b.last);
+      if (checksum) ip += 4;
+    }
+    return count;
+  });
   m.def("hash_columns_cpu", &hash_columns_cpu);
   m.def("hash_string_column_cpu", &hash_string_column_cpu);
   m.def("bucket_ids_from_hashes", &bucket_ids_from_hashes);

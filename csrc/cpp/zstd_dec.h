@@ -4,10 +4,19 @@
 // RLE / FSE / repeat sequence tables, repeat offsets, multi-block
 // frames; no dictionaries, no checksum verification).
 //
-// Written to be portable into a HIP kernel: no STL containers in the
-// decode path, fixed-size scratch tables, plain C-style code. The host
-// build is differential-tested against libzstd on real parquet pages
-// (tests/test_zstd_dec.py); the device port lives in csrc/hip/zstd.hip.
+// Shared with the GPU kernel (csrc/hip/zstd.hip), which includes this
+// file: the bit readers, the FSE / huffman table builders and every
+// function that knows the layout of a frame (frame, block and literals
+// headers, huffman tree description, 4-stream layout, sequence count,
+// sequence tables, one sequence). Those are LSZ_HD, pure functions of the
+// input bytes and small lane-uniform state: they move no output bytes and
+// never synchronise. Per side: the byte movement and its fencing — the
+// host drivers at the end of this file use memcpy, the device drivers use
+// wave-cooperative copies. No STL containers in the decode path,
+// fixed-size scratch tables, plain C-style code. The host build is
+// differential-tested against libzstd on real parquet pages
+// (tests/test_zstd_dec.py), so the device's parse and bounds checks carry
+// that coverage too.
 //
 // This replaces host-side libzstd in the GPU scan path so page
 // decompression scales with the GPU instead of the (cgroup-capped) CPU
@@ -149,10 +158,21 @@ struct FseTable {  // no default initializers: instances live in LDS
   uint8_t rleSym;
 };
 
+// table-build workspace. The host keeps one in Ctx, the device one in LDS
+// for lane 0 (dynamically-indexed locals would otherwise force a multi-KB
+// private segment per lane that craters wave residency).
+struct BuildWs {
+  FseTable wt;                         // huffman-weight FSE table
+  int16_t counts[kMaxSymbols];         // normalized counts
+  uint16_t symNext[kMaxSymbols];
+  uint8_t symTab[1 << kMaxTableLog];
+  uint8_t weights[kMaxSymbols];        // huffman weights
+};
+
 // read normalized counts (RFC 8878 4.1.1) from a forward bitstream.
 // returns max symbol (inclusive) or -1 on error.
-LSZ_COLD inline int fse_read_ncount(BitFwd& br, int16_t* counts, int maxSymLimit,
-                                  int& tableLog) {
+LSZ_HD inline int fse_read_ncount_br(BitFwd& br, int16_t* counts,
+                                     int maxSymLimit, int& tableLog) {
   tableLog = (int)br.read(4) + 5;
   if (tableLog > kMaxTableLog) return -1;
   int32_t remaining = (1 << tableLog) + 1;
@@ -199,12 +219,31 @@ LSZ_COLD inline int fse_read_ncount(BitFwd& br, int16_t* counts, int maxSymLimit
   return sym - 1;
 }
 
-// build a decode table from normalized counts (FSE_buildDTable).
-// symTab/symbolNext are caller scratch (>= 512 / 256 entries) so the
-// device build can keep them in LDS instead of per-lane scratch memory.
-LSZ_COLD inline bool fse_build(FseTable& t, const int16_t* counts, int maxSym,
-                               int tableLog, uint8_t* symTab,
-                               uint16_t* symbolNext) {
+struct NCount {
+  int maxSym;        // -1 on error
+  int tableLog;
+  int64_t consumed;  // bytes of the description
+};
+
+// the same from src[0..n). Returns by value, so that on the device (where
+// this is not inlined) the bit reader lives in this function's frame and
+// not in the kernel's private segment.
+LSZ_COLD inline NCount fse_read_ncount(const uint8_t* src, int64_t n,
+                                       int16_t* counts, int maxSymLimit) {
+  BitFwd br{src, n};
+  NCount r;
+  r.maxSym = fse_read_ncount_br(br, counts, maxSymLimit, r.tableLog);
+  r.consumed = br.bytes_consumed();
+  return r;
+}
+
+// build a decode table from the normalized counts in ws.counts
+// (FSE_buildDTable)
+LSZ_COLD inline bool fse_build(FseTable& t, int maxSym, int tableLog,
+                               BuildWs& ws) {
+  const int16_t* counts = ws.counts;
+  uint8_t* symTab = ws.symTab;
+  uint16_t* symbolNext = ws.symNext;
   t.tableLog = tableLog;
   t.rle = false;
   int tableSize = 1 << tableLog;
@@ -242,13 +281,6 @@ LSZ_COLD inline bool fse_build(FseTable& t, const int16_t* counts, int maxSym,
   return true;
 }
 
-LSZ_HD inline bool fse_build(FseTable& t, const int16_t* counts, int maxSym,
-                             int tableLog) {
-  uint8_t symTab[1 << kMaxTableLog];
-  uint16_t symbolNext[kMaxSymbols];
-  return fse_build(t, counts, maxSym, tableLog, symTab, symbolNext);
-}
-
 LSZ_HD inline void fse_build_rle(FseTable& t, uint8_t sym) {
   t.rle = true;
   t.rleSym = sym;
@@ -273,18 +305,15 @@ struct FseState {
 
 // generic FSE decompression (used for huffman weights): strict s1/s2
 // alternation, stop after overflow emits the final symbol (libzstd
-// FSE_decompress_usingDTable tail semantics)
+// FSE_decompress_usingDTable tail semantics). dst must not alias ws.wt /
+// ws.counts / ws.symTab / ws.symNext; ws.weights is fine.
 LSZ_COLD inline int fse_decompress_ws(const uint8_t* src, int64_t n, uint8_t* dst,
-                                    int dstCap, FseTable& table,
-                                    int16_t* counts, uint8_t* symTab,
-                                    uint16_t* symbolNext) {
-  BitFwd hdr{src, n};
-  int tableLog;
-  int maxSym = fse_read_ncount(hdr, counts, 255, tableLog);
-  if (maxSym < 0) return -1;
-  if (!fse_build(table, counts, maxSym, tableLog, symTab, symbolNext))
-    return -1;
-  int64_t consumed = hdr.bytes_consumed();
+                                    int dstCap, BuildWs& ws) {
+  FseTable& table = ws.wt;
+  NCount nc = fse_read_ncount(src, n, ws.counts, 255);
+  if (nc.maxSym < 0) return -1;
+  if (!fse_build(table, nc.maxSym, nc.tableLog, ws)) return -1;
+  int64_t consumed = nc.consumed;
   BitBwd br;
   if (!br.init(src + consumed, n - consumed)) return -1;
   FseState s1, s2;
@@ -310,16 +339,6 @@ LSZ_COLD inline int fse_decompress_ws(const uint8_t* src, int64_t n, uint8_t* ds
     }
   }
   return out;
-}
-
-LSZ_HD inline int fse_decompress(const uint8_t* src, int64_t n, uint8_t* dst,
-                                 int dstCap) {
-  FseTable table;
-  int16_t counts[kMaxSymbols];
-  uint8_t symTab[1 << kMaxTableLog];
-  uint16_t symbolNext[kMaxSymbols];
-  return fse_decompress_ws(src, n, dst, dstCap, table, counts, symTab,
-                           symbolNext);
 }
 
 // ---------------------------------------------------------------------- //
@@ -463,194 +482,363 @@ LSZ_HD inline void predef_of(int16_t* c, int& maxSym, int& tlog) {
 }
 
 // ---------------------------------------------------------------------- //
-// decoder context (persists across blocks within a frame)
+// format parse functions, shared by the host and device drivers. Each is
+// a pure function of the input bytes (and lane-uniform state): no output
+// bytes, no synchronisation. Those that build a table write it; the
+// device calls only those on a single lane.
 // ---------------------------------------------------------------------- //
 
+// frame or skippable-frame header at src[ip] (caller checked ip + 4 <= n).
+// Returns the new ip (past a skippable frame, or at the first block
+// header) or -1.
+LSZ_HD inline int64_t parse_frame_header(const uint8_t* src, int64_t n,
+                                         int64_t ip, bool& skippable,
+                                         bool& checksum) {
+  uint32_t magic;
+  memcpy(&magic, src + ip, 4);
+  checksum = false;
+  skippable = (magic & 0xFFFFFFF0u) == 0x184D2A50u;
+  if (skippable) {
+    if (ip + 8 > n) return -1;
+    uint32_t sz;
+    memcpy(&sz, src + ip + 4, 4);
+    return ip + 8 + (int64_t)sz;  // 64-bit: a 32-bit sum wraps to ip + 0
+  }
+  if (magic != kMagic) return -1;
+  ip += 4;
+  if (ip >= n) return -1;
+  uint8_t fhd = src[ip++];
+  int fcsFlag = fhd >> 6;
+  bool singleSeg = (fhd >> 5) & 1;
+  checksum = (fhd >> 2) & 1;
+  int dictFlag = fhd & 3;
+  if (!singleSeg) {
+    if (ip >= n) return -1;
+    ip++;  // window descriptor (we size by dstCap)
+  }
+  ip += (1 << dictFlag) >> 1;  // dictionary id: 0, 1, 2 or 4 bytes
+  // content size (informative only): 0/1, 2, 4 or 8 bytes
+  ip += fcsFlag == 0 ? (singleSeg ? 1 : 0) : (1 << fcsFlag);
+  return ip > n ? -1 : ip;
+}
+
+enum { kBlockRaw = 0, kBlockRle = 1, kBlockCompressed = 2 };
+
+struct BlockHdr {
+  bool last;
+  int type;
+  int64_t size;      // raw / RLE: regenerated bytes; compressed: input bytes
+  int64_t srcBytes;  // input bytes that follow the 3-byte header
+};
+
+// block header at p; fails on the reserved type and when the block's input
+// bytes do not fit in rem
+LSZ_HD inline bool parse_block_header(const uint8_t* p, int64_t rem,
+                                      BlockHdr& h) {
+  if (rem < 3) return false;
+  uint32_t bh = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+  h.last = bh & 1;
+  h.type = (bh >> 1) & 3;
+  h.size = bh >> 3;
+  h.srcBytes = h.type == kBlockRle ? 1 : h.size;
+  return h.type != 3 && 3 + h.srcBytes <= rem;
+}
+
+enum { kLitRaw = 0, kLitRle = 1, kLitCompressed = 2, kLitTreeless = 3 };
+
+struct LitHdr {
+  int type;
+  int sizeFormat;  // the 2-bit header form
+  int nStreams;    // huffman streams (compressed / treeless)
+  int64_t rs;      // regenerated size
+  int64_t cs;      // input bytes after the header (raw: rs, RLE: 1)
+  int64_t hdr;     // header length
+};
+
+// literals-section header; checks hdr + cs <= n. The caller checks rs
+// against its literals buffer.
+LSZ_HD inline bool parse_literals_header(const uint8_t* src, int64_t n,
+                                         LitHdr& h) {
+  if (n < 1) return false;
+  h.type = src[0] & 3;
+  h.sizeFormat = (src[0] >> 2) & 3;
+  h.nStreams = 1;
+  if (h.type == kLitRaw || h.type == kLitRle) {
+    if ((h.sizeFormat & 1) == 0) {           // 00 or 10: 5-bit size
+      h.rs = src[0] >> 3;
+      h.hdr = 1;
+    } else if (h.sizeFormat == 1) {          // 01: 12-bit
+      if (n < 2) return false;
+      h.rs = (src[0] >> 4) | ((int64_t)src[1] << 4);
+      h.hdr = 2;
+    } else {                                 // 11: 20-bit
+      if (n < 3) return false;
+      h.rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)src[2] << 12);
+      h.hdr = 3;
+    }
+    h.cs = h.type == kLitRaw ? h.rs : 1;
+  } else if (h.sizeFormat <= 1) {  // 1 stream (00) or 4 streams (01), 10-bit
+    if (n < 3) return false;
+    h.rs = (src[0] >> 4) | ((int64_t)(src[1] & 0x3F) << 4);
+    h.cs = (src[1] >> 6) | ((int64_t)src[2] << 2);
+    h.hdr = 3;
+    h.nStreams = h.sizeFormat == 0 ? 1 : 4;
+  } else if (h.sizeFormat == 2) {  // 4 streams, 14-bit
+    if (n < 4) return false;
+    h.rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 3) << 12);
+    h.cs = (src[2] >> 2) | ((int64_t)src[3] << 6);
+    h.hdr = 4;
+    h.nStreams = 4;
+  } else {  // 4 streams, 18-bit
+    if (n < 5) return false;
+    h.rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 0x3F) << 12);
+    h.cs = (src[2] >> 6) | ((int64_t)src[3] << 2) | ((int64_t)src[4] << 10);
+    h.hdr = 5;
+    h.nStreams = 4;
+  }
+  return h.hdr + h.cs <= n;
+}
+
+// first byte of a huffman tree description: direct 4-bit weights, or
+// FSE-compressed weights
+LSZ_HD inline bool huf_desc_direct(uint8_t hb) { return hb >= 128; }
+
+// huffman tree description at p: weights into ws, decode table into t.
+// Returns bytes consumed or -1.
+LSZ_HD inline int64_t read_huf_tree(const uint8_t* p, int64_t rem,
+                                    HufTable& t, BuildWs& ws) {
+  if (rem < 1) return -1;
+  uint8_t hb = p[0];
+  int nw;
+  int64_t used;
+  if (huf_desc_direct(hb)) {
+    nw = hb - 127;
+    used = 1 + (nw + 1) / 2;
+    if (used > rem) return -1;
+    for (int i = 0; i < nw; i++) {
+      uint8_t b = p[1 + i / 2];
+      ws.weights[i] = (i & 1) ? (b & 0xF) : (b >> 4);
+    }
+  } else {
+    used = 1 + hb;
+    if (used > rem) return -1;
+    nw = fse_decompress_ws(p + 1, hb, ws.weights, 255, ws);
+    if (nw < 0) return -1;
+  }
+  return huf_build(t, ws.weights, nw) ? used : -1;
+}
+
+struct HufStream {
+  int64_t start, len;        // input bytes p[start .. start + len)
+  int64_t outStart, outLen;  // its slice of the rs regenerated bytes
+};
+
+// stream i (0-3) of a 4-stream literals payload: the jump table at p and
+// the output split. Whether it fails does not depend on i. (Selects, not
+// indexed arrays: the device calls this with i = lane, and an indexed
+// local would go to per-lane scratch memory.)
+LSZ_HD inline bool huf4_stream(const uint8_t* p, int64_t rem, int64_t rs, int i,
+                               HufStream& s) {
+  if (rem < 6) return false;
+  int64_t s1 = p[0] | ((int64_t)p[1] << 8);
+  int64_t s2 = p[2] | ((int64_t)p[3] << 8);
+  int64_t s3 = p[4] | ((int64_t)p[5] << 8);
+  int64_t s4 = rem - 6 - s1 - s2 - s3;
+  int64_t o123 = (rs + 3) / 4;
+  int64_t o4 = rs - 3 * o123;
+  if (s4 < 0 || o4 < 0) return false;
+  s.start = 6 + (i > 0 ? s1 : 0) + (i > 1 ? s2 : 0) + (i > 2 ? s3 : 0);
+  s.len = i == 0 ? s1 : i == 1 ? s2 : i == 2 ? s3 : s4;
+  s.outStart = i * o123;
+  s.outLen = i == 3 ? o4 : o123;
+  return true;
+}
+
+// number of sequences (1/2/3-byte forms). Returns bytes consumed or -1.
+LSZ_HD inline int read_seq_count(const uint8_t* p, int64_t rem, int64_t& nSeq) {
+  if (rem < 1) return -1;
+  if (p[0] < 128) {
+    nSeq = p[0];
+    return 1;
+  }
+  if (p[0] < 255) {
+    if (rem < 2) return -1;
+    nSeq = ((int64_t)(p[0] - 128) << 8) + p[1];
+    return 2;
+  }
+  if (rem < 3) return -1;
+  nSeq = p[1] + ((int64_t)p[2] << 8) + 0x7F00;
+  return 3;
+}
+
+enum { kSeqLL = 0, kSeqOF = 1, kSeqML = 2 };  // table kinds
+enum { kModePredef = 0, kModeRle = 1, kModeFse = 2, kModeRepeat = 3 };
+
+// 2-bit mode of table `kind` in the symbol-compression-modes byte
+LSZ_HD inline int seq_mode(uint8_t modes, int kind) {
+  return (modes >> (6 - 2 * kind)) & 3;
+}
+
+// the three sequence decode tables; persist across the blocks of a frame
+struct SeqTables {  // no default initializers: instances live in LDS
+  FseTable t[3];    // indexed by kind
+  bool have[3];
+};
+
+// read the table of `kind` per its mode. Returns bytes consumed, -1 err.
+// Repeat mode writes nothing. (Inlined on the device too: as a call it
+// cost sorted int64 pages about 1 % of their decode time.)
+LSZ_HD inline int64_t read_seq_table(SeqTables& st, int kind, int mode,
+                                     const uint8_t* src, int64_t n,
+                                     BuildWs& ws) {
+  const int maxSymLimit = kind == kSeqLL ? 35 : kind == kSeqOF ? 31 : 52;
+  FseTable& t = st.t[kind];
+  if (mode == kModeRepeat) return st.have[kind] ? 0 : -1;
+  int64_t used = 0;
+  if (mode == kModeRle) {  // 1 byte symbol
+    if (n < 1 || src[0] > maxSymLimit) return -1;
+    fse_build_rle(t, src[0]);
+    used = 1;
+  } else {
+    int maxSym, tlog;
+    if (mode == kModePredef) {
+      if (kind == kSeqLL) predef_ll(ws.counts, maxSym, tlog);
+      else if (kind == kSeqOF) predef_of(ws.counts, maxSym, tlog);
+      else predef_ml(ws.counts, maxSym, tlog);
+    } else {  // FSE table description
+      NCount nc = fse_read_ncount(src, n, ws.counts, maxSymLimit);
+      if (nc.maxSym < 0) return -1;
+      maxSym = nc.maxSym;
+      tlog = nc.tableLog;
+      used = nc.consumed;
+    }
+    if (!fse_build(t, maxSym, tlog, ws)) return -1;
+  }
+  st.have[kind] = true;
+  return used;
+}
+
+struct SeqStates {
+  FseState s[3];  // indexed by kind
+  LSZ_HD void init(const SeqTables& st, BitBwd& br) {
+    s[kSeqLL].init(st.t[kSeqLL], br);
+    s[kSeqOF].init(st.t[kSeqOF], br);
+    s[kSeqML].init(st.t[kSeqML], br);
+  }
+  // between sequences (not after the last one)
+  LSZ_HD void update(const SeqTables& st, BitBwd& br) {
+    s[kSeqLL].update(st.t[kSeqLL], br);
+    s[kSeqML].update(st.t[kSeqML], br);
+    s[kSeqOF].update(st.t[kSeqOF], br);
+  }
+};
+
+struct Seq {
+  uint32_t litLen, matchLen, offset;
+};
+
+// decode the sequence the states point at: three symbols, their extra
+// bits, and the repeat-offset rules (updates rep)
+LSZ_HD inline Seq next_sequence(const SeqTables& st, const SeqStates& ss,
+                                BitBwd& br, uint32_t* rep) {
+  int ofCode = ss.s[kSeqOF].symbol(st.t[kSeqOF]);
+  int mlCode = ss.s[kSeqML].symbol(st.t[kSeqML]);
+  int llCode = ss.s[kSeqLL].symbol(st.t[kSeqLL]);
+
+  uint32_t ofValue = (ofCode ? (1u << ofCode) : 1u) + br.read(ofCode);
+  Seq q;
+  CodeExtra mle = ml_extra(mlCode);
+  q.matchLen = mle.base + br.read(mle.bits);
+  CodeExtra lle = ll_extra(llCode);
+  q.litLen = lle.base + br.read(lle.bits);
+
+  if (ofValue > 3) {
+    q.offset = ofValue - 3;
+    rep[2] = rep[1];
+    rep[1] = rep[0];
+    rep[0] = q.offset;
+  } else {
+    uint32_t idx = ofValue - 1 + (q.litLen == 0 ? 1 : 0);
+    if (idx == 0) {
+      q.offset = rep[0];
+    } else {
+      uint32_t tmp = (idx == 3) ? rep[0] - 1 : rep[idx];
+      if (tmp == 0) tmp = 1;  // corner case per libzstd
+      if (idx != 1) rep[2] = rep[1];
+      rep[1] = rep[0];
+      rep[0] = tmp;
+      q.offset = tmp;
+    }
+  }
+  return q;
+}
+
+// ---------------------------------------------------------------------- //
+// host drivers: parse with the functions above, move bytes with memcpy
+// ---------------------------------------------------------------------- //
+
+// decoder context (tables persist across blocks within a frame)
 struct Ctx {
-  FseTable ll, of, ml;
-  bool haveLl = false, haveOf = false, haveMl = false;
+  SeqTables seq;
   HufTable huf;
   bool haveHuf = false;
   uint32_t rep[3] = {1, 4, 8};
+  BuildWs ws;
   uint8_t litBuf[1 << 17];   // ≤128 KB literals per block
 };
 
 // decode literals section; returns bytes consumed from src or -1.
 // litLen receives the regenerated length (data in ctx.litBuf).
-LSZ_HD inline int64_t decode_literals(Ctx& ctx, const uint8_t* src, int64_t n,
-                                      int64_t& litLen) {
-  if (n < 1) return -1;
-  int type = src[0] & 3;
-  int sizeFormat = (src[0] >> 2) & 3;
-  if (type == 0 || type == 1) {  // Raw / RLE
-    int64_t rs;
-    int64_t hdr;
-    if ((sizeFormat & 1) == 0) {           // 00 or 10: 5-bit size
-      rs = src[0] >> 3;
-      hdr = 1;
-    } else if (sizeFormat == 1) {          // 01: 12-bit
-      if (n < 2) return -1;
-      rs = (src[0] >> 4) | ((int64_t)src[1] << 4);
-      hdr = 2;
-    } else {                               // 11: 20-bit
-      if (n < 3) return -1;
-      rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)src[2] << 12);
-      hdr = 3;
-    }
-    if (rs > (int64_t)sizeof(ctx.litBuf)) return -1;
-    litLen = rs;
-    if (type == 0) {
-      if (hdr + rs > n) return -1;
-      memcpy(ctx.litBuf, src + hdr, (size_t)rs);
-      return hdr + rs;
-    }
-    if (hdr + 1 > n) return -1;
-    memset(ctx.litBuf, src[hdr], (size_t)rs);
-    return hdr + 1;
-  }
-  // Compressed (2) / Treeless (3)
-  int64_t rs, cs, hdr;
-  int nStreams;
-  if (sizeFormat == 0) {  // 1 stream, 10-bit sizes
-    if (n < 3) return -1;
-    rs = (src[0] >> 4) | ((int64_t)(src[1] & 0x3F) << 4);
-    cs = (src[1] >> 6) | ((int64_t)src[2] << 2);
-    hdr = 3;
-    nStreams = 1;
-  } else if (sizeFormat == 1) {  // 4 streams, 10-bit
-    if (n < 3) return -1;
-    rs = (src[0] >> 4) | ((int64_t)(src[1] & 0x3F) << 4);
-    cs = (src[1] >> 6) | ((int64_t)src[2] << 2);
-    hdr = 3;
-    nStreams = 4;
-  } else if (sizeFormat == 2) {  // 4 streams, 14-bit
-    if (n < 4) return -1;
-    rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 3) << 12);
-    cs = (src[2] >> 2) | ((int64_t)src[3] << 6);
-    hdr = 4;
-    nStreams = 4;
-  } else {  // 4 streams, 18-bit
-    if (n < 5) return -1;
-    rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 0x3F) << 12);
-    cs = (src[2] >> 6) | ((int64_t)src[3] << 2) | ((int64_t)src[4] << 10);
-    hdr = 5;
-    nStreams = 4;
-  }
-  if (rs > (int64_t)sizeof(ctx.litBuf) || hdr + cs > n) return -1;
-  litLen = rs;
-  const uint8_t* p = src + hdr;
-  int64_t rem = cs;
-
-  if (type == 2) {  // huffman description present
-    if (rem < 1) return -1;
-    uint8_t hb = p[0];
-    uint8_t weights[256];
-    int nw;
-    if (hb >= 128) {  // direct 4-bit weights
-      nw = hb - 127;
-      int64_t wb = (nw + 1) / 2;
-      if (1 + wb > rem) return -1;
-      for (int i = 0; i < nw; i++) {
-        uint8_t b = p[1 + i / 2];
-        weights[i] = (i & 1) ? (b & 0xF) : (b >> 4);
-      }
-      p += 1 + wb;
-      rem -= 1 + wb;
-    } else {  // FSE-compressed weights
-      if (1 + hb > rem) return -1;
-      nw = fse_decompress(p + 1, hb, weights, 255);
-      if (nw < 0) return -1;
-      p += 1 + hb;
-      rem -= 1 + hb;
-    }
-    if (!huf_build(ctx.huf, weights, nw)) return -1;
-    ctx.haveHuf = true;
-  } else if (!ctx.haveHuf) {
-    return -1;  // treeless without a previous table
-  }
-
-  if (nStreams == 1) {
-    if (!huf_stream(ctx.huf, p, rem, ctx.litBuf, rs)) return -1;
+inline int64_t decode_literals(Ctx& ctx, const uint8_t* src, int64_t n,
+                               int64_t& litLen) {
+  LitHdr h;
+  if (!parse_literals_header(src, n, h)) return -1;
+  if (h.rs > (int64_t)sizeof(ctx.litBuf)) return -1;
+  litLen = h.rs;
+  const uint8_t* p = src + h.hdr;
+  if (h.type == kLitRaw) {
+    memcpy(ctx.litBuf, p, (size_t)h.rs);
+  } else if (h.type == kLitRle) {
+    memset(ctx.litBuf, p[0], (size_t)h.rs);
   } else {
-    if (rem < 6) return -1;
-    int64_t s1 = p[0] | ((int64_t)p[1] << 8);
-    int64_t s2 = p[2] | ((int64_t)p[3] << 8);
-    int64_t s3 = p[4] | ((int64_t)p[5] << 8);
-    int64_t s4 = rem - 6 - s1 - s2 - s3;
-    if (s4 < 0) return -1;
-    int64_t o123 = (rs + 3) / 4;
-    int64_t o4 = rs - 3 * o123;
-    if (o4 < 0) return -1;
-    const uint8_t* q = p + 6;
-    if (!huf_stream(ctx.huf, q, s1, ctx.litBuf, o123)) return -1;
-    if (!huf_stream(ctx.huf, q + s1, s2, ctx.litBuf + o123, o123)) return -1;
-    if (!huf_stream(ctx.huf, q + s1 + s2, s3, ctx.litBuf + 2 * o123, o123))
-      return -1;
-    if (!huf_stream(ctx.huf, q + s1 + s2 + s3, s4, ctx.litBuf + 3 * o123, o4))
-      return -1;
+    int64_t rem = h.cs;
+    if (h.type == kLitCompressed) {  // huffman description present
+      int64_t used = read_huf_tree(p, rem, ctx.huf, ctx.ws);
+      if (used < 0) return -1;
+      ctx.haveHuf = true;
+      p += used;
+      rem -= used;
+    } else if (!ctx.haveHuf) {
+      return -1;  // treeless without a previous table
+    }
+    if (h.nStreams == 1) {
+      if (!huf_stream(ctx.huf, p, rem, ctx.litBuf, h.rs)) return -1;
+    } else {
+      for (int i = 0; i < 4; i++) {
+        HufStream s;
+        if (!huf4_stream(p, rem, h.rs, i, s)) return -1;
+        if (!huf_stream(ctx.huf, p + s.start, s.len, ctx.litBuf + s.outStart,
+                        s.outLen))
+          return -1;
+      }
+    }
   }
-  return hdr + cs;
-}
-
-// read one sequence table per its 2-bit mode. Returns bytes consumed, -1 err.
-LSZ_HD inline int64_t read_seq_table(Ctx& ctx, FseTable& t, bool& have,
-                                     int mode, const uint8_t* src, int64_t n,
-                                     void (*predef)(int16_t*, int&, int&),
-                                     int maxSymLimit) {
-  if (mode == 0) {  // predefined
-    int16_t c[64];
-    int maxSym, tlog;
-    predef(c, maxSym, tlog);
-    if (!fse_build(t, c, maxSym, tlog)) return -1;
-    have = true;
-    return 0;
-  }
-  if (mode == 1) {  // RLE: 1 byte symbol
-    if (n < 1) return -1;
-    if (src[0] > maxSymLimit) return -1;
-    fse_build_rle(t, src[0]);
-    have = true;
-    return 1;
-  }
-  if (mode == 2) {  // FSE table description
-    BitFwd br{src, n};
-    int16_t c[64];
-    int tlog;
-    int maxSym = fse_read_ncount(br, c, maxSymLimit, tlog);
-    if (maxSym < 0) return -1;
-    if (!fse_build(t, c, maxSym, tlog)) return -1;
-    have = true;
-    return br.bytes_consumed();
-  }
-  // repeat
-  return have ? 0 : -1;
+  return h.hdr + h.cs;
 }
 
 // decode one compressed block into dst (history = dst window start..pos)
-LSZ_HD inline int64_t decode_block(Ctx& ctx, const uint8_t* src, int64_t n,
-                                   uint8_t* dstBase, int64_t pos,
-                                   int64_t dstCap) {
+inline int64_t decode_block(Ctx& ctx, const uint8_t* src, int64_t n,
+                            uint8_t* dstBase, int64_t pos, int64_t dstCap) {
   int64_t litLen;
-  int64_t c = decode_literals(ctx, src, n, litLen);
-  if (c < 0) return -1;
-  const uint8_t* p = src + c;
-  int64_t rem = n - c;
+  int64_t used = decode_literals(ctx, src, n, litLen);
+  if (used < 0) return -1;
+  const uint8_t* p = src + used;
+  int64_t rem = n - used;
 
-  // sequences header
-  if (rem < 1) return -1;
   int64_t nSeq;
-  if (p[0] < 128) {
-    nSeq = p[0];
-    p += 1; rem -= 1;
-  } else if (p[0] < 255) {
-    if (rem < 2) return -1;
-    nSeq = ((int64_t)(p[0] - 128) << 8) + p[1];
-    p += 2; rem -= 2;
-  } else {
-    if (rem < 3) return -1;
-    nSeq = p[1] + ((int64_t)p[2] << 8) + 0x7F00;
-    p += 3; rem -= 3;
-  }
+  used = read_seq_count(p, rem, nSeq);
+  if (used < 0) return -1;
+  p += used; rem -= used;
 
   if (nSeq == 0) {
     if (pos + litLen > dstCap) return -1;
@@ -659,86 +847,45 @@ LSZ_HD inline int64_t decode_block(Ctx& ctx, const uint8_t* src, int64_t n,
   }
 
   if (rem < 1) return -1;
-  int modes = p[0];
+  uint8_t modes = p[0];
   p += 1; rem -= 1;
-  int llMode = (modes >> 6) & 3, ofMode = (modes >> 4) & 3,
-      mlMode = (modes >> 2) & 3;
-
-  int64_t used;
-  used = read_seq_table(ctx, ctx.ll, ctx.haveLl, llMode, p, rem, predef_ll, 35);
-  if (used < 0) return -1;
-  p += used; rem -= used;
-  used = read_seq_table(ctx, ctx.of, ctx.haveOf, ofMode, p, rem, predef_of, 31);
-  if (used < 0) return -1;
-  p += used; rem -= used;
-  used = read_seq_table(ctx, ctx.ml, ctx.haveMl, mlMode, p, rem, predef_ml, 52);
-  if (used < 0) return -1;
-  p += used; rem -= used;
+  for (int kind = kSeqLL; kind <= kSeqML; kind++) {
+    used = read_seq_table(ctx.seq, kind, seq_mode(modes, kind), p, rem, ctx.ws);
+    if (used < 0) return -1;
+    p += used; rem -= used;
+  }
 
   // execute sequences from the backward bitstream
   BitBwd br;
   if (!br.init(p, rem)) return -1;
-  FseState sLl, sOf, sMl;
-  sLl.init(ctx.ll, br);
-  sOf.init(ctx.of, br);
-  sMl.init(ctx.ml, br);
+  SeqStates ss;
+  ss.init(ctx.seq, br);
 
   int64_t litPos = 0;
   int64_t out = pos;
   for (int64_t s = 0; s < nSeq; s++) {
-    int ofCode = sOf.symbol(ctx.of);
-    int mlCode = sMl.symbol(ctx.ml);
-    int llCode = sLl.symbol(ctx.ll);
-
-    uint32_t ofValue = (ofCode ? (1u << ofCode) : 1u) + br.read(ofCode);
-    CodeExtra mle = ml_extra(mlCode);
-    uint32_t matchLen = mle.base + br.read(mle.bits);
-    CodeExtra lle = ll_extra(llCode);
-    uint32_t litLenSeq = lle.base + br.read(lle.bits);
-
-    // repeat-offset resolution
-    uint32_t offset;
-    if (ofValue > 3) {
-      offset = ofValue - 3;
-      ctx.rep[2] = ctx.rep[1];
-      ctx.rep[1] = ctx.rep[0];
-      ctx.rep[0] = offset;
-    } else {
-      uint32_t idx = ofValue - 1 + (litLenSeq == 0 ? 1 : 0);
-      if (idx == 0) {
-        offset = ctx.rep[0];
-      } else {
-        uint32_t tmp = (idx == 3) ? ctx.rep[0] - 1 : ctx.rep[idx];
-        if (tmp == 0) tmp = 1;  // corner case per libzstd
-        if (idx != 1) ctx.rep[2] = ctx.rep[1];
-        ctx.rep[1] = ctx.rep[0];
-        ctx.rep[0] = tmp;
-        offset = tmp;
-      }
-    }
+    Seq q = next_sequence(ctx.seq, ss, br, ctx.rep);
 
     // copy literals
-    if (litPos + litLenSeq > litLen || out + litLenSeq > dstCap) return -1;
-    memcpy(dstBase + out, ctx.litBuf + litPos, litLenSeq);
-    litPos += litLenSeq;
-    out += litLenSeq;
+    if (litPos + q.litLen > litLen || out + q.litLen > dstCap) return -1;
+    memcpy(dstBase + out, ctx.litBuf + litPos, q.litLen);
+    litPos += q.litLen;
+    out += q.litLen;
     // copy match (may overlap)
-    if ((int64_t)offset > out || out + matchLen > dstCap) return -1;
+    if ((int64_t)q.offset > out || out + q.matchLen > dstCap) return -1;
     {
-      const uint8_t* from = dstBase + out - offset;
+      const uint8_t* from = dstBase + out - q.offset;
       uint8_t* to = dstBase + out;
-      if (offset >= matchLen) {
-        memcpy(to, from, matchLen);
+      if (q.offset >= q.matchLen) {
+        memcpy(to, from, q.matchLen);
       } else {
-        for (uint32_t i = 0; i < matchLen; i++) to[i] = from[i];
+        for (uint32_t i = 0; i < q.matchLen; i++) to[i] = from[i];
       }
-      out += matchLen;
+      out += q.matchLen;
     }
 
     if (s + 1 < nSeq) {  // last sequence: no state update
-      sLl.update(ctx.ll, br);
-      sMl.update(ctx.ml, br);
-      sOf.update(ctx.of, br);
+      ss.update(ctx.seq, br);
       if (br.overflow) return -1;
     }
   }
@@ -751,76 +898,37 @@ LSZ_HD inline int64_t decode_block(Ctx& ctx, const uint8_t* src, int64_t n,
 }
 
 // decode a full zstd frame sequence. Returns decompressed size or -1.
-LSZ_HD inline int64_t decode(const uint8_t* src, int64_t n, uint8_t* dst,
-                             int64_t dstCap, Ctx* ctx) {
+inline int64_t decode(const uint8_t* src, int64_t n, uint8_t* dst,
+                      int64_t dstCap, Ctx* ctx) {
   int64_t pos = 0;        // output position
   int64_t ip = 0;
   while (ip + 4 <= n) {
-    uint32_t magic;
-    memcpy(&magic, src + ip, 4);
-    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // skippable frame
-      if (ip + 8 > n) return -1;
-      uint32_t sz;
-      memcpy(&sz, src + ip + 4, 4);
-      ip += 8 + sz;
-      continue;
-    }
-    if (magic != kMagic) return -1;
-    ip += 4;
-    if (ip >= n) return -1;
-    uint8_t fhd = src[ip++];
-    int fcsFlag = fhd >> 6;
-    bool singleSeg = (fhd >> 5) & 1;
-    bool checksum = (fhd >> 2) & 1;
-    int dictFlag = fhd & 3;
-    if (!singleSeg) {
-      if (ip >= n) return -1;
-      ip++;  // window descriptor (we size by dstCap)
-    }
-    static const int dictLen[4] = {0, 1, 2, 4};
-    ip += dictLen[dictFlag];
-    int fcsLen = 0;
-    if (fcsFlag == 0) fcsLen = singleSeg ? 1 : 0;
-    else if (fcsFlag == 1) fcsLen = 2;
-    else if (fcsFlag == 2) fcsLen = 4;
-    else fcsLen = 8;
-    ip += fcsLen;  // content size informative only
-    if (ip > n) return -1;
+    bool skippable, checksum;
+    ip = parse_frame_header(src, n, ip, skippable, checksum);
+    if (ip < 0) return -1;
+    if (skippable) continue;
 
     // reset inter-block context per frame
-    ctx->haveLl = ctx->haveOf = ctx->haveMl = false;
+    ctx->seq.have[0] = ctx->seq.have[1] = ctx->seq.have[2] = false;
     ctx->haveHuf = false;
     ctx->rep[0] = 1; ctx->rep[1] = 4; ctx->rep[2] = 8;
 
-    bool last = false;
-    while (!last) {
-      if (ip + 3 > n) return -1;
-      uint32_t bh = src[ip] | ((uint32_t)src[ip + 1] << 8) |
-                    ((uint32_t)src[ip + 2] << 16);
+    BlockHdr b;
+    do {
+      if (!parse_block_header(src + ip, n - ip, b)) return -1;
       ip += 3;
-      last = bh & 1;
-      int btype = (bh >> 1) & 3;
-      int64_t bsize = bh >> 3;
-      if (btype == 0) {  // raw
-        if (ip + bsize > n || pos + bsize > dstCap) return -1;
-        memcpy(dst + pos, src + ip, (size_t)bsize);
-        ip += bsize;
-        pos += bsize;
-      } else if (btype == 1) {  // RLE
-        if (ip + 1 > n || pos + bsize > dstCap) return -1;
-        memset(dst + pos, src[ip], (size_t)bsize);
-        ip += 1;
-        pos += bsize;
-      } else if (btype == 2) {
-        if (ip + bsize > n) return -1;
-        int64_t outb = decode_block(*ctx, src + ip, bsize, dst, pos, dstCap);
+      if (b.type == kBlockCompressed) {
+        int64_t outb = decode_block(*ctx, src + ip, b.size, dst, pos, dstCap);
         if (outb < 0) return -1;
-        ip += bsize;
         pos += outb;
       } else {
-        return -1;
+        if (pos + b.size > dstCap) return -1;
+        if (b.type == kBlockRaw) memcpy(dst + pos, src + ip, (size_t)b.size);
+        else memset(dst + pos, src[ip], (size_t)b.size);
+        pos += b.size;
       }
-    }
+      ip += b.srcBytes;
+    } while (!b.last);
     if (checksum) ip += 4;
   }
   return pos;

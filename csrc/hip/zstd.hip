@@ -1,7 +1,13 @@
 // GPU zstd page decompressor (gfx950): one wave64 workgroup per parquet
-// page, grid-stride over pages. Decode logic is shared with the host
-// reference implementation (csrc/cpp/zstd_dec.h, differential-tested
-// against libzstd); this file adds the CDNA4 execution strategy:
+// page, grid-stride over pages. Shared with the host reference
+// implementation (csrc/cpp/zstd_dec.h, differential-tested against
+// libzstd): the bit readers, the FSE / huffman table builders and every
+// format parse function (frame, block and literals headers, huffman tree
+// description, 4-stream layout, sequence count, sequence tables, one
+// sequence). Every lane calls the parse functions on the same bytes, so
+// their results and every early return are lane-uniform; the ones that
+// build a table run on lane 0 only. This file holds what is per-side —
+// the byte movement and its fencing, i.e. the CDNA4 execution strategy:
 //
 // - every lane runs the *sequential* control flow redundantly in
 //   lockstep (same bytes, same results — no broadcasts, no divergence);
@@ -91,39 +97,46 @@ __device__ inline void wfill(uint8_t* dst, uint8_t v, int64_t len, int lane) {
 }
 
 struct LdsCtx {
-  FseTable ll, of, ml;
+  SeqTables seq;
   HufTable huf;
-  int haveLl, haveOf, haveMl, haveHuf;
+  bool haveHuf;
   int64_t scratch_i64;     // lane0 -> wave value handoff
-  int16_t counts[64];      // ncount output (seq tables)
-  uint8_t weights[256];    // huffman weights
-  int scratch_i32;
-  // lane0 table-build workspaces (LDS, not per-lane scratch memory —
+  // lane0 table-build workspace (LDS, not per-lane scratch memory —
   // dynamically-indexed locals would otherwise force a multi-KB private
   // segment that craters wave residency)
-  FseTable wt;             // huffman-weight FSE table
-  int16_t wcounts[256];
-  uint8_t symTab[1 << kMaxTableLog];
-  uint16_t symNext[256];
+  BuildWs ws;
   // rolling window of the last 32 output bytes (win[31] most recent).
   // Matches with offset <= 32 read ONLY this window: no global reads,
   // no fences — the serial cost per sequence collapses to LDS ops.
   uint8_t win[32];
 };
 
+// window <- last 32 bytes of (window ++ run): BYTE_AT is an expression in
+// k (int64_t) that yields byte k of the n-byte appended run. Every lane
+// reads its new byte before any lane writes; SYNC orders the two (and
+// follows the write): __syncthreads, or lds_sync inside the sequence loop.
+// A macro, not a function taking a callable: through a function the
+// compiler laid the in-loop sites out with two more LDS reads and four
+// more LDS waits per sequence (3.6 % slower on sorted int64 pages).
+#define WIN_SLIDE(c, n, lane, SYNC, BYTE_AT)                          \
+  do {                                                                \
+    uint8_t nb_ = 0;                                                  \
+    if ((lane) < 32) {                                                \
+      int64_t w_ = (int64_t)(lane) + (n); /* index into window ++ run */ \
+      int64_t k = w_ - 32;                                            \
+      nb_ = (w_ < 32) ? (c).win[w_] : (BYTE_AT);                      \
+    }                                                                 \
+    SYNC();                                                           \
+    if ((lane) < 32) (c).win[lane] = nb_;                             \
+    SYNC();                                                           \
+  } while (0)
+
 // slide `src[0..n)` into the 32-byte window (volatile read: src may be
 // wave-written global memory that has been fenced)
 __device__ inline void win_append_from(LdsCtx& c, const uint8_t* src,
                                        int64_t n, int lane) {
   if (n <= 0) return;
-  uint8_t nb = 0;
-  if (lane < 32) {
-    int64_t k = (int64_t)lane + n;
-    nb = (k < 32) ? c.win[k] : ((volatile const uint8_t*)src)[k - 32];
-  }
-  __syncthreads();
-  if (lane < 32) c.win[lane] = nb;
-  __syncthreads();
+  WIN_SLIDE(c, n, lane, __syncthreads, ((volatile const uint8_t*)src)[k]);
 }
 
 __device__ inline void win_fill(LdsCtx& c, uint8_t v, int lane) {
@@ -137,168 +150,62 @@ __device__ inline void win_fill(LdsCtx& c, uint8_t v, int lane) {
 __device__ inline int64_t dev_literals(LdsCtx& c, uint8_t* lit,
                                        const uint8_t* src, int64_t n,
                                        int64_t& litLen, int lane) {
-  if (n < 1) return -1;
-  int type = src[0] & 3;
-  int sizeFormat = (src[0] >> 2) & 3;
-  if (type == 0 || type == 1) {  // Raw / RLE
-    int64_t rs, hdr;
-    if ((sizeFormat & 1) == 0) {
-      rs = src[0] >> 3;
-      hdr = 1;
-    } else if (sizeFormat == 1) {
-      if (n < 2) return -1;
-      rs = (src[0] >> 4) | ((int64_t)src[1] << 4);
-      hdr = 2;
-    } else {
-      if (n < 3) return -1;
-      rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)src[2] << 12);
-      hdr = 3;
-    }
-    if (rs > kLitBufCap) return -1;
-    litLen = rs;
-    if (type == 0) {
-      if (hdr + rs > n) return -1;
-      wcopy_src(lit, src + hdr, rs, lane);
-      return hdr + rs;
-    }
-    if (hdr + 1 > n) return -1;
-    wfill(lit, src[hdr], rs, lane);
-    return hdr + 1;
+  LitHdr h;
+  if (!parse_literals_header(src, n, h)) return -1;
+  if (h.rs > kLitBufCap) return -1;
+  litLen = h.rs;
+  const uint8_t* p = src + h.hdr;
+  if (h.type == kLitRaw) {
+    wcopy_src(lit, p, h.rs, lane);
+    return h.hdr + h.cs;
   }
-  // Compressed (2) / Treeless (3)
-  int64_t rs, cs, hdr;
-  int nStreams;
-  if (sizeFormat == 0) {
-    if (n < 3) return -1;
-    rs = (src[0] >> 4) | ((int64_t)(src[1] & 0x3F) << 4);
-    cs = (src[1] >> 6) | ((int64_t)src[2] << 2);
-    hdr = 3;
-    nStreams = 1;
-  } else if (sizeFormat == 1) {
-    if (n < 3) return -1;
-    rs = (src[0] >> 4) | ((int64_t)(src[1] & 0x3F) << 4);
-    cs = (src[1] >> 6) | ((int64_t)src[2] << 2);
-    hdr = 3;
-    nStreams = 4;
-  } else if (sizeFormat == 2) {
-    if (n < 4) return -1;
-    rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 3) << 12);
-    cs = (src[2] >> 2) | ((int64_t)src[3] << 6);
-    hdr = 4;
-    nStreams = 4;
-  } else {
-    if (n < 5) return -1;
-    rs = (src[0] >> 4) | ((int64_t)src[1] << 4) | ((int64_t)(src[2] & 0x3F) << 12);
-    cs = (src[2] >> 6) | ((int64_t)src[3] << 2) | ((int64_t)src[4] << 10);
-    hdr = 5;
-    nStreams = 4;
+  if (h.type == kLitRle) {
+    wfill(lit, p[0], h.rs, lane);
+    return h.hdr + h.cs;
   }
-  if (rs > kLitBufCap || hdr + cs > n) return -1;
-  litLen = rs;
-  const uint8_t* p = src + hdr;
-  int64_t rem = cs;
-
-  if (type == 2) {
-    if (rem < 1) return -1;
-    uint8_t hb = p[0];
+  int64_t rem = h.cs;
+  if (h.type == kLitCompressed) {
     // weights parse + table build on lane 0 only (keeps the 256-byte
     // weights array and FSE decode state out of per-lane scratch)
     if (lane == 0) {
-      int nw = -1;
-      int64_t consumed = -1;
-      if (hb >= 128) {
-        nw = hb - 127;
-        int64_t wb = (nw + 1) / 2;
-        if (1 + wb <= rem) {
-          for (int i = 0; i < nw; i++) {
-            uint8_t b = p[1 + i / 2];
-            c.weights[i] = (i & 1) ? (b & 0xF) : (b >> 4);
-          }
-          consumed = 1 + wb;
-        }
-      } else if (1 + hb <= rem) {
-        nw = fse_decompress_ws(p + 1, hb, c.weights, 255, c.wt, c.wcounts,
-                               c.symTab, c.symNext);
-        consumed = 1 + hb;
-      }
-      bool ok = consumed >= 0 && nw >= 0 && huf_build(c.huf, c.weights, nw);
-      c.haveHuf = ok ? 1 : -1;
-      c.scratch_i64 = consumed;
+      int64_t used = read_huf_tree(p, rem, c.huf, c.ws);
+      if (used >= 0) c.haveHuf = true;
+      c.scratch_i64 = used;
     }
     __syncthreads();
-    if (c.haveHuf < 0) return -1;
+    if (c.scratch_i64 < 0) return -1;
     p += c.scratch_i64;
     rem -= c.scratch_i64;
     __syncthreads();
-  } else if (c.haveHuf != 1) {
+  } else if (!c.haveHuf) {
     return -1;
   }
 
   bool ok = true;
-  if (nStreams == 1) {
-    if (lane == 0) ok = huf_stream(c.huf, p, rem, lit, rs);
+  if (h.nStreams == 1) {
+    if (lane == 0) ok = huf_stream(c.huf, p, rem, lit, h.rs);
   } else {
-    if (rem < 6) return -1;
-    int64_t s1 = p[0] | ((int64_t)p[1] << 8);
-    int64_t s2 = p[2] | ((int64_t)p[3] << 8);
-    int64_t s3 = p[4] | ((int64_t)p[5] << 8);
-    int64_t s4 = rem - 6 - s1 - s2 - s3;
-    if (s4 < 0) return -1;
-    int64_t o123 = (rs + 3) / 4;
-    int64_t o4 = rs - 3 * o123;
-    if (o4 < 0) return -1;
-    const uint8_t* q = p + 6;
-    if (lane < 4) {
-      // one shared decode instance: lanes 0-3 each take a stream
-      int64_t starts[4] = {0, s1, s1 + s2, s1 + s2 + s3};
-      int64_t lens[4] = {s1, s2, s3, s4};
-      ok = huf_stream(c.huf, q + starts[lane], lens[lane], lit + lane * o123,
-                      lane == 3 ? o4 : o123);
-    }
+    HufStream s;
+    if (!huf4_stream(p, rem, h.rs, lane & 3, s)) return -1;
+    if (lane < 4)  // one shared decode instance: lanes 0-3 each take a stream
+      ok = huf_stream(c.huf, p + s.start, s.len, lit + s.outStart, s.outLen);
   }
   waitcnt0();
   __syncthreads();
   if (__ballot(!ok)) return -1;
-  return hdr + cs;
+  return h.hdr + h.cs;
 }
 
-__device__ inline int64_t dev_read_seq_table(
-    LdsCtx& c, FseTable& t, int& have, int mode, const uint8_t* src, int64_t n,
-    int which, int maxSymLimit, int lane) {  // which: 0=LL 1=OF 2=ML
-  if (mode == 0) {
-    if (lane == 0) {
-      int maxSym, tlog;
-      if (which == 0) predef_ll(c.counts, maxSym, tlog);
-      else if (which == 1) predef_of(c.counts, maxSym, tlog);
-      else predef_ml(c.counts, maxSym, tlog);
-      have = fse_build(t, c.counts, maxSym, tlog, c.symTab, c.symNext) ? 1 : -1;
-    }
-    __syncthreads();
-    return have < 0 ? -1 : 0;
-  }
-  if (mode == 1) {
-    if (n < 1 || src[0] > maxSymLimit) return -1;
-    if (lane == 0) {
-      fse_build_rle(t, src[0]);
-      have = 1;
-    }
-    __syncthreads();
-    return 1;
-  }
-  if (mode == 2) {
-    if (lane == 0) {
-      BitFwd br{src, n};
-      int tlog;
-      int maxSym = fse_read_ncount(br, c.counts, maxSymLimit, tlog);
-      bool ok = maxSym >= 0 &&
-                fse_build(t, c.counts, maxSym, tlog, c.symTab, c.symNext);
-      have = ok ? 1 : -1;
-      c.scratch_i64 = br.bytes_consumed();
-    }
-    __syncthreads();
-    return have < 0 ? -1 : c.scratch_i64;
-  }
-  return have == 1 ? 0 : -1;
+// one sequence table: lane 0 builds it in LDS and hands the bytes
+// consumed to the wave. Repeat mode builds nothing, so every lane
+// evaluates it and there is no handoff and no barrier.
+__device__ inline int64_t dev_read_seq_table(LdsCtx& c, int kind, int mode,
+                                             const uint8_t* src, int64_t n,
+                                             int lane) {
+  if (mode == kModeRepeat) return read_seq_table(c.seq, kind, mode, src, n, c.ws);
+  if (lane == 0) c.scratch_i64 = read_seq_table(c.seq, kind, mode, src, n, c.ws);
+  __syncthreads();
+  return c.scratch_i64;
 }
 
 // one compressed block; every lane in lockstep
@@ -307,25 +214,15 @@ __device__ inline int64_t dev_block(LdsCtx& c, uint8_t* lit, uint32_t* rep,
                                     uint8_t* dstBase, int64_t pos,
                                     int64_t dstCap, int lane) {
   int64_t litLen;
-  int64_t consumed = dev_literals(c, lit, src, n, litLen, lane);
-  if (consumed < 0) return -1;
-  const uint8_t* p = src + consumed;
-  int64_t rem = n - consumed;
+  int64_t used = dev_literals(c, lit, src, n, litLen, lane);
+  if (used < 0) return -1;
+  const uint8_t* p = src + used;
+  int64_t rem = n - used;
 
-  if (rem < 1) return -1;
   int64_t nSeq;
-  if (p[0] < 128) {
-    nSeq = p[0];
-    p += 1; rem -= 1;
-  } else if (p[0] < 255) {
-    if (rem < 2) return -1;
-    nSeq = ((int64_t)(p[0] - 128) << 8) + p[1];
-    p += 2; rem -= 2;
-  } else {
-    if (rem < 3) return -1;
-    nSeq = p[1] + ((int64_t)p[2] << 8) + 0x7F00;
-    p += 3; rem -= 3;
-  }
+  used = read_seq_count(p, rem, nSeq);
+  if (used < 0) return -1;
+  p += used; rem -= used;
 
   if (nSeq == 0) {
     if (pos + litLen > dstCap) return -1;
@@ -335,28 +232,18 @@ __device__ inline int64_t dev_block(LdsCtx& c, uint8_t* lit, uint32_t* rep,
   }
 
   if (rem < 1) return -1;
-  int modes = p[0];
+  uint8_t modes = p[0];
   p += 1; rem -= 1;
-  int llMode = (modes >> 6) & 3, ofMode = (modes >> 4) & 3,
-      mlMode = (modes >> 2) & 3;
-
-  int64_t used;
-  used = dev_read_seq_table(c, c.ll, c.haveLl, llMode, p, rem, 0, 35, lane);
-  if (used < 0) return -1;
-  p += used; rem -= used;
-  used = dev_read_seq_table(c, c.of, c.haveOf, ofMode, p, rem, 1, 31, lane);
-  if (used < 0) return -1;
-  p += used; rem -= used;
-  used = dev_read_seq_table(c, c.ml, c.haveMl, mlMode, p, rem, 2, 52, lane);
-  if (used < 0) return -1;
-  p += used; rem -= used;
+  for (int kind = kSeqLL; kind <= kSeqML; kind++) {
+    used = dev_read_seq_table(c, kind, seq_mode(modes, kind), p, rem, lane);
+    if (used < 0) return -1;
+    p += used; rem -= used;
+  }
 
   BitBwd br;
   if (!br.init(p, rem)) return -1;
-  FseState sLl, sOf, sMl;
-  sLl.init(c.ll, br);
-  sOf.init(c.of, br);
-  sMl.init(c.ml, br);
+  SeqStates ss;
+  ss.init(c.seq, br);
 
   // W = everything below this output position is store-fence'd (visible
   // to plain/GLC reads); advance lazily, fencing only when a large-offset
@@ -365,51 +252,16 @@ __device__ inline int64_t dev_block(LdsCtx& c, uint8_t* lit, uint32_t* rep,
   int64_t litPos = 0;
   int64_t out = pos;
   for (int64_t s = 0; s < nSeq; s++) {
-    int ofCode = sOf.symbol(c.of);
-    int mlCode = sMl.symbol(c.ml);
-    int llCode = sLl.symbol(c.ll);
-
-    uint32_t ofValue = (ofCode ? (1u << ofCode) : 1u) + br.read(ofCode);
-    CodeExtra mle = ml_extra(mlCode);
-    uint32_t matchLen = mle.base + br.read(mle.bits);
-    CodeExtra lle = ll_extra(llCode);
-    uint32_t litLenSeq = lle.base + br.read(lle.bits);
-
-    uint32_t offset;
-    if (ofValue > 3) {
-      offset = ofValue - 3;
-      rep[2] = rep[1];
-      rep[1] = rep[0];
-      rep[0] = offset;
-    } else {
-      uint32_t idx = ofValue - 1 + (litLenSeq == 0 ? 1 : 0);
-      if (idx == 0) {
-        offset = rep[0];
-      } else {
-        uint32_t tmp = (idx == 3) ? rep[0] - 1 : rep[idx];
-        if (tmp == 0) tmp = 1;
-        if (idx != 1) rep[2] = rep[1];
-        rep[1] = rep[0];
-        rep[0] = tmp;
-        offset = tmp;
-      }
-    }
+    Seq q = next_sequence(c.seq, ss, br, rep);
+    uint32_t litLenSeq = q.litLen, matchLen = q.matchLen, offset = q.offset;
 
     // ---- literals: litBuf reads are hazard-free (fenced after the
     // literals phase); dst writes are fire-and-forget ----
     if (litPos + litLenSeq > litLen || out + litLenSeq > dstCap) return -1;
     if (litLenSeq) {
       wcopy_wide<true>(dstBase + out, lit + litPos, litLenSeq, lane);
-      // window <- last 32 bytes of (window ++ literals)
-      uint8_t nb = 0;
-      if (lane < 32) {
-        int64_t k = (int64_t)lane + litLenSeq;   // index into win ++ lits
-        nb = (k < 32) ? c.win[k]
-                      : ((volatile const uint8_t*)lit)[litPos + (k - 32)];
-      }
-      lds_sync();
-      if (lane < 32) c.win[lane] = nb;
-      lds_sync();
+      WIN_SLIDE(c, litLenSeq, lane, lds_sync,
+                ((volatile const uint8_t*)lit)[litPos + k]);
       litPos += litLenSeq;
       out += litLenSeq;
     }
@@ -420,15 +272,8 @@ __device__ inline int64_t dev_block(LdsCtx& c, uint8_t* lit, uint32_t* rep,
       // source is entirely inside the register window: no global reads
       for (uint32_t j = lane; j < matchLen; j += LANES)
         dstBase[out + j] = c.win[(32 - offset) + (j % offset)];
-      uint8_t nb = 0;
-      if (lane < 32) {
-        int64_t k = (int64_t)lane + matchLen;
-        nb = (k < 32) ? c.win[k]
-                      : c.win[(32 - offset) + (uint32_t)((k - 32) % offset)];
-      }
-      lds_sync();
-      if (lane < 32) c.win[lane] = nb;
-      lds_sync();
+      WIN_SLIDE(c, matchLen, lane, lds_sync,
+                c.win[(32 - offset) + (uint32_t)(k % offset)]);
     } else {
       // large offset: source bytes live below `out`; fence once if they
       // reach into the unfenced region
@@ -440,24 +285,14 @@ __device__ inline int64_t dev_block(LdsCtx& c, uint8_t* lit, uint32_t* rep,
       for (uint32_t j = lane; j < matchLen; j += LANES)
         dstBase[out + j] =
             ((volatile const uint8_t*)dstBase)[out - offset + (j % offset)];
-      uint8_t nb = 0;
-      if (lane < 32) {
-        int64_t k = (int64_t)lane + matchLen;
-        nb = (k < 32)
-                 ? c.win[k]
-                 : ((volatile const uint8_t*)
-                        dstBase)[out - offset + (uint32_t)((k - 32) % offset)];
-      }
-      lds_sync();
-      if (lane < 32) c.win[lane] = nb;
-      lds_sync();
+      WIN_SLIDE(c, matchLen, lane, lds_sync,
+                ((volatile const uint8_t*)
+                     dstBase)[out - offset + (uint32_t)(k % offset)]);
     }
     out += matchLen;
 
-    if (s + 1 < nSeq) {
-      sLl.update(c.ll, br);
-      sMl.update(c.ml, br);
-      sOf.update(c.of, br);
+    if (s + 1 < nSeq) {  // last sequence: no state update
+      ss.update(c.seq, br);
       if (br.overflow) return -1;
     }
   }
@@ -475,83 +310,45 @@ __device__ inline int64_t dev_frame(LdsCtx& c, uint8_t* lit, const uint8_t* src,
   int64_t pos = 0, ip = 0;
   uint32_t rep[3];
   while (ip + 4 <= n) {
-    uint32_t magic;
-    memcpy(&magic, src + ip, 4);
-    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
-      if (ip + 8 > n) return -1;
-      uint32_t sz;
-      memcpy(&sz, src + ip + 4, 4);
-      ip += 8 + sz;
-      continue;
-    }
-    if (magic != kMagic) return -1;
-    ip += 4;
-    if (ip >= n) return -1;
-    uint8_t fhd = src[ip++];
-    int fcsFlag = fhd >> 6;
-    bool singleSeg = (fhd >> 5) & 1;
-    bool checksum = (fhd >> 2) & 1;
-    int dictFlag = fhd & 3;
-    if (!singleSeg) {
-      if (ip >= n) return -1;
-      ip++;
-    }
-    const int dictLen[4] = {0, 1, 2, 4};
-    ip += dictLen[dictFlag];
-    int fcsLen = (fcsFlag == 0) ? (singleSeg ? 1 : 0)
-                                : (fcsFlag == 1 ? 2 : (fcsFlag == 2 ? 4 : 8));
-    ip += fcsLen;
-    if (ip > n) return -1;
+    bool skippable, checksum;
+    ip = parse_frame_header(src, n, ip, skippable, checksum);
+    if (ip < 0) return -1;
+    if (skippable) continue;
 
-    if (lane == 0) { c.haveLl = c.haveOf = c.haveMl = 0; c.haveHuf = 0; }
+    if (lane == 0) {
+      c.seq.have[0] = c.seq.have[1] = c.seq.have[2] = false;
+      c.haveHuf = false;
+    }
     if (lane < 32) c.win[lane] = 0;
     __syncthreads();
     rep[0] = 1; rep[1] = 4; rep[2] = 8;
 
-    bool last = false;
-    while (!last) {
-      if (ip + 3 > n) return -1;
-      uint32_t bh = src[ip] | ((uint32_t)src[ip + 1] << 8) |
-                    ((uint32_t)src[ip + 2] << 16);
+    BlockHdr b;
+    do {
+      if (!parse_block_header(src + ip, n - ip, b)) return -1;
       ip += 3;
-      last = bh & 1;
-      int btype = (bh >> 1) & 3;
-      int64_t bsize = bh >> 3;
-      if (btype == 0) {
-        if (ip + bsize > n || pos + bsize > dstCap) return -1;
-        wcopy_src(dst + pos, src + ip, bsize, lane);
-        win_append_from(c, src + ip, bsize, lane);
-        ip += bsize;
-        pos += bsize;
-      } else if (btype == 1) {
-        if (ip + 1 > n || pos + bsize > dstCap) return -1;
-        wfill(dst + pos, src[ip], bsize, lane);
-        if (bsize >= 32) {
-          win_fill(c, src[ip], lane);
-        } else {
-          uint8_t v = src[ip];
-          uint8_t nb = 0;
-          if (lane < 32) {
-            int64_t k = (int64_t)lane + bsize;
-            nb = (k < 32) ? c.win[k] : v;
-          }
-          __syncthreads();
-          if (lane < 32) c.win[lane] = nb;
-          __syncthreads();
-        }
-        ip += 1;
-        pos += bsize;
-      } else if (btype == 2) {
-        if (ip + bsize > n) return -1;
-        int64_t outb = dev_block(c, lit, rep, src + ip, bsize, dst, pos,
+      if (b.type == kBlockCompressed) {
+        int64_t outb = dev_block(c, lit, rep, src + ip, b.size, dst, pos,
                                  dstCap, lane);
         if (outb < 0) return -1;
-        ip += bsize;
         pos += outb;
       } else {
-        return -1;
+        if (pos + b.size > dstCap) return -1;
+        if (b.type == kBlockRaw) {
+          wcopy_src(dst + pos, src + ip, b.size, lane);
+          win_append_from(c, src + ip, b.size, lane);
+        } else {
+          uint8_t v = src[ip];
+          wfill(dst + pos, v, b.size, lane);
+          if (b.size >= 32)
+            win_fill(c, v, lane);
+          else
+            WIN_SLIDE(c, b.size, lane, __syncthreads, ((void)k, v));
+        }
+        pos += b.size;
       }
-    }
+      ip += b.srcBytes;
+    } while (!b.last);
     if (checksum) ip += 4;
   }
   return pos;

@@ -549,6 +549,34 @@ def test_gpu_zstd_kernel_matches_reference(dev):
 
 
 @pytest.mark.gpu
+def test_gpu_zstd_corpus(dev):
+    """The corpus of tests/zstd_corpus.py (test_zstd_dec.py asserts which
+    format features it exercises, hand-assembled RLE-literals frames
+    included) as one jobs table and one launch: every status is 0 and the
+    output bytes equal the originals."""
+    from lakesoul_amd.ops import hip
+    from zstd_corpus import corpus
+
+    entries = corpus()
+    src = torch.from_numpy(np.frombuffer(
+        b"".join(c for _, c, _ in entries), dtype=np.uint8).copy()).to(dev)
+    expect = b"".join(o for _, _, o in entries)
+    dst = torch.zeros(len(expect), dtype=torch.uint8, device=dev)
+    jobs = []
+    so = do = 0
+    for _, c, o in entries:
+        jobs.append([so, len(c), do, len(o)])
+        so += len(c)
+        do += len(o)
+    jt = torch.tensor(jobs, dtype=torch.int64, device=dev)
+    status = hip().zstd_decompress_into(src, jt, dst)
+    torch.cuda.synchronize()
+    bad = [entries[i][0] for i in status.cpu().nonzero().flatten().tolist()]
+    assert not bad, f"non-zero status: {bad[:10]}"
+    assert dst.cpu().numpy().tobytes() == expect
+
+
+@pytest.mark.gpu
 def test_gpu_zstd_scan_path_active(dev, tmp_path, monkeypatch):
     """End-to-end MOR scan with the GPU zstd path opted in: results equal
     the CPU scan, and the unit fetch reports zstd jobs (not host decode)."""
