@@ -291,6 +291,10 @@ def _apply_op_gpu(f, col: Column, op: str, order, grp, ngroups, seq_sorted,
         if col.is_string:
             raise TypeError("sum merge operator on string column")
         data_sorted = col.data[order]
+        if data_sorted.dtype in (torch.int16, torch.int8):
+            # the kernel sums int32 at the narrowest; .to(col.data.dtype)
+            # below wraps to the column's width as the CPU merge does
+            data_sorted = data_sorted.to(torch.int32)
         if op == "SumLast":
             los = torch.zeros(n, dtype=torch.bool, device=device)
             if n:

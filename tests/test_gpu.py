@@ -27,19 +27,146 @@ def test_murmur3_fixed_gpu_matches_cpu(dev):
     from lakesoul_amd.ops import hip
     from lakesoul_amd.utils import murmur3 as m3
 
+    from lakesoul_amd.utils import murmur3_np
+
     rng = np.random.default_rng(0)
     empty_prev = torch.empty(0, dtype=torch.int64, device=dev)
     empty_val = torch.empty(0, dtype=torch.uint8, device=dev)
-    for dt, name in [(np.int64, "int64"), (np.int32, "int32"),
-                     (np.float32, "float32"), (np.float64, "float64")]:
-        if dt in (np.int64, np.int32):
-            vals = rng.integers(-10**9, 10**9, 1000).astype(dt)
-        else:
-            vals = rng.normal(size=1000).astype(dt)
+    for name in _HASH_DTYPES:
+        vals = _hash_values(rng, name)
         t = torch.from_numpy(vals).to(dev)
+        if name == "bool":
+            t = t.to(torch.bool)
         h = hip().hash_fixed_column(t, empty_val, empty_prev, True).cpu().numpy()
-        for i in range(0, 1000, 131):
+        # every row against the numpy murmur3, some against the scalar one
+        want = murmur3_np.hash_column(vals, murmur3_np.HASH_SEED)
+        np.testing.assert_array_equal(h, want.astype(np.int64), err_msg=name)
+        if name == "uint8":
+            continue  # no scalar rule of its own: a byte hashes as its value
+        for i in list(range(12)) + list(range(12, len(vals), 131)):
             assert int(h[i]) == m3.hash_value(vals[i].item(), name), (name, i)
+        # chained: the previous hash is the seed
+        h2 = hip().hash_fixed_column(t, empty_val, torch.from_numpy(h).to(dev),
+                                     False).cpu().numpy()
+        np.testing.assert_array_equal(
+            h2, murmur3_np.hash_column(vals, want).astype(np.int64), err_msg=name)
+
+
+_HASH_DTYPES = ["bool", "uint8", "int8", "int16", "int32", "int64", "float32",
+                "float64"]
+
+
+def _hash_values(rng, name):
+    """The type's min and max, -1 and 0 first (for floats also both zeros,
+    NaN, both infinities and a denormal), then the whole range at random."""
+    if name == "bool":
+        return np.array([0, 1] * 6 + list(rng.integers(0, 2, 1000)), dtype=np.bool_)
+    dt = np.dtype(name)
+    if dt.kind == "f":
+        fi = np.finfo(dt)
+        head = [fi.min, fi.max, -1.0, 0.0, -0.0, np.nan, np.inf, -np.inf,
+                fi.smallest_subnormal, -fi.smallest_subnormal, fi.tiny, 1.0]
+        body = rng.normal(size=1000) * 10.0 ** rng.integers(-30, 30, 1000)
+        return np.concatenate([np.array(head, dtype=dt), body.astype(dt)])
+    ii = np.iinfo(dt)
+    head = [ii.min, ii.max, -1 if ii.min < 0 else ii.max, 0, 1, ii.min + 1,
+            ii.max - 1, 127 if ii.max >= 128 else 1, 128 if ii.max >= 128 else 0,
+            ii.max // 2, 2, 3]
+    body = rng.integers(ii.min, ii.max, 1000, dtype=dt, endpoint=True)
+    return np.concatenate([np.array(head, dtype=dt), body])
+
+
+@pytest.mark.parametrize("names", [("int64", "int32"),
+                                   ("int16", "float64", "int8")],
+                         ids=["two_columns", "three_columns"])
+def test_murmur3_validity_gpu(dev, names):
+    """A null in the first column hashes to 0; a null in a chained column
+    leaves the running hash as it is. Nulls in every position of a two-
+    and a three-column key, against both CPU implementations."""
+    from lakesoul_amd.ops import hip
+    from lakesoul_amd.utils import murmur3 as m3
+    from lakesoul_amd.utils.murmur3_np import create_hashes_np
+
+    rng = np.random.default_rng(20)
+    cols = [_hash_values(rng, name)[:600] for name in names]
+    n = len(cols[0])
+    masks = [rng.random(n) < 0.7 for _ in names]
+    # every combination of null and non-null across the columns
+    for r in range(2 ** len(names)):
+        for c in range(len(names)):
+            masks[c][r] = bool(r >> c & 1)
+    h = torch.empty(0, dtype=torch.int64, device=dev)
+    for ci, (col, mask) in enumerate(zip(cols, masks)):
+        prev = h
+        h = hip().hash_fixed_column(
+            torch.from_numpy(col).to(dev),
+            torch.from_numpy(mask.astype(np.uint8)).to(dev), prev, ci == 0)
+        got, null = h.cpu().numpy(), ~mask
+        if ci == 0:
+            assert (got[null] == 0).all()
+        else:
+            np.testing.assert_array_equal(got[null], prev.cpu().numpy()[null])
+    got = h.cpu().numpy()
+    want = create_hashes_np(cols, valid_masks=masks)
+    np.testing.assert_array_equal(got, want.astype(np.int64))
+    scalar = m3.create_hashes(
+        [[v.item() if ok else None for v, ok in zip(col, mask)]
+         for col, mask in zip(cols, masks)], list(names))
+    assert got.tolist() == scalar
+
+
+def test_murmur3_string_tails_gpu(dev):
+    """Lengths 0-9 and 31-33 with bytes from the whole 0-255 range, so
+    that tails of 1, 2 and 3 bytes hold values >= 0x80: every row against
+    murmur3.hash_bytes, first and chained, with and without nulls."""
+    from lakesoul_amd.ops import hip
+    from lakesoul_amd.utils import murmur3 as m3
+
+    rng = np.random.default_rng(21)
+    lens = list(range(10)) + [31, 32, 33]
+    rows = [b"\xff" * n for n in lens] + [b"\x80" * n for n in lens]
+    rows += [rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+             for n in lens for _ in range(20)]
+    rows += [rng.integers(128, 256, n, dtype=np.uint8).tobytes()
+             for n in (1, 2, 3, 5, 6, 7, 33) for _ in range(5)]
+    n = len(rows)
+    offs = np.zeros(n + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([len(r) for r in rows])
+    by = np.frombuffer(b"".join(rows), dtype=np.uint8).copy()
+    offs_t, by_t = torch.from_numpy(offs).to(dev), torch.from_numpy(by).to(dev)
+    empty_prev = torch.empty(0, dtype=torch.int64, device=dev)
+    empty_val = torch.empty(0, dtype=torch.uint8, device=dev)
+    valid = rng.random(n) < 0.7
+    valid_t = torch.from_numpy(valid.astype(np.uint8)).to(dev)
+    prev = rng.integers(0, 2 ** 32, n)   # running hashes, some >= 2**31
+    prev_t = torch.from_numpy(prev).to(dev)
+
+    got = hip().hash_string_column(offs_t, by_t, empty_val, empty_prev, True)
+    assert got.cpu().tolist() == [m3.hash_bytes(r) for r in rows]
+    got = hip().hash_string_column(offs_t, by_t, valid_t, empty_prev, True)
+    assert got.cpu().tolist() == [m3.hash_bytes(r) if ok else 0
+                                  for r, ok in zip(rows, valid)]
+    got = hip().hash_string_column(offs_t, by_t, empty_val, prev_t, False)
+    assert got.cpu().tolist() == [m3.hash_bytes(r, int(p))
+                                  for r, p in zip(rows, prev)]
+    got = hip().hash_string_column(offs_t, by_t, valid_t, prev_t, False)
+    assert got.cpu().tolist() == [m3.hash_bytes(r, int(p)) if ok else int(p)
+                                  for r, p, ok in zip(rows, prev, valid)]
+
+
+@pytest.mark.parametrize("nb", [1, 3, 16, 1000])
+def test_bucket_ids_gpu(dev, nb):
+    """Hashes are unsigned 32-bit values held in int64: those >= 2**31
+    must not turn negative on the way to the bucket."""
+    from lakesoul_amd.ops import hip
+
+    rng = np.random.default_rng(22)
+    h = np.concatenate([
+        np.array([0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1, 2 ** 32 - 1]),
+        rng.integers(0, 2 ** 32, 2000)]).astype(np.int64)
+    assert (h >= 2 ** 31).sum() > 500
+    got = hip().bucket_ids(torch.from_numpy(h).to(dev), nb).cpu().numpy()
+    np.testing.assert_array_equal(got, h % nb)
 
 
 def test_murmur3_string_and_chaining_gpu(dev):
@@ -59,13 +186,11 @@ def test_murmur3_string_and_chaining_gpu(dev):
     )
     ids = torch.arange(500, dtype=torch.int64, device=dev)
     h2 = hip().hash_fixed_column(ids, empty_val, h1, False)
-    got = h2.cpu().numpy()
-    for i in range(0, 500, 61):
-        expect = m3.hash_int64(i, m3.hash_str(strings[i]))
-        assert int(got[i]) == expect
+    assert h1.cpu().tolist() == [m3.hash_str(s) for s in strings]
+    expect = [m3.hash_int64(i, m3.hash_str(s)) for i, s in enumerate(strings)]
+    assert h2.cpu().tolist() == expect
     b = hip().bucket_ids(h2, 16).cpu().numpy()
-    for i in range(0, 500, 61):
-        assert b[i] == m3.hash_int64(i, m3.hash_str(strings[i])) % 16
+    assert b.tolist() == [e % 16 for e in expect]
 
 
 def test_merge_pairs_kernel(dev):
@@ -113,31 +238,48 @@ def test_merge_sorted_keys_matches_stable_sort(dev, lens):
     np.testing.assert_array_equal(keys.cpu().numpy(), concat[expect])
 
 
-@pytest.mark.parametrize("stored", ["int64", "int32", "float64"])
-def test_rle_dict_decode_gpu_vs_pyarrow(dev, tmp_path, stored):
-    """Dictionary chunks through the production decoder (read_unit_raw ->
-    UnitTransfer -> decode_unit). A PLAIN column precedes the dictionary
-    column, so the dict payload sits at a non-zero offset of the values
-    buffer; es = 4 and 8 both take the dict path."""
+def _write_dict_file(path, stored, card, n=50000):
+    """A parquet file with a PLAIN column ``a`` and a dictionary column
+    ``c`` of ``card`` distinct values, 10% nulls and a stretch of 4000
+    equal values, so that repeat runs and bit-packed runs alternate.
+    Returns (values as written, valid mask)."""
     import pyarrow as pa
     import pyarrow.parquet as pq
 
+    rng = np.random.default_rng(2)
+    cat = (rng.integers(0, card, n) * 7).astype(np.int64)
+    cat[:card] = np.arange(card) * 7     # the first row group uses them all
+    cat[23000:27000] = cat[23000]
+    valid = rng.random(n) >= 0.1
+    pa_type = {"int64": pa.int64(), "int32": pa.int32(),
+               "float64": pa.float64()}[stored]
+    want = cat.astype(stored)
+    tbl = pa.table({"a": pa.array(np.arange(n, dtype=np.int64)),
+                    "c": pa.array(want, type=pa_type, mask=~valid)})
+    pq.write_table(tbl, str(path), use_dictionary=["c"], compression="zstd",
+                   row_group_size=20000)
+    assert pq.ParquetFile(str(path)).metadata.num_row_groups == 3
+    # nulls may hide a few entries; the index bit width is still card's
+    used = len(np.unique(want[:20000][valid[:20000]]))
+    assert (used - 1).bit_length() == (card - 1).bit_length()
+    return want, valid
+
+
+@pytest.mark.parametrize("stored", ["int64", "int32", "float64"])
+@pytest.mark.parametrize("card", [1, 2, 3, 17, 100, 300, 5000])
+def test_rle_dict_decode_gpu_vs_pyarrow(dev, tmp_path, stored, card):
+    """Dictionary chunks through the production decoder (read_unit_raw ->
+    UnitTransfer -> decode_unit). A PLAIN column precedes the dictionary
+    column, so the dict payload sits at a non-zero offset of the values
+    buffer; es = 4 and 8 both take the dict path. Dictionaries of 1, 2, 3,
+    17, 100, 300 and 5000 values give index bit widths 0, 1, 2, 5, 7, 9
+    and 13."""
     from lakesoul_amd.io.reader_gpu import UnitTransfer
     from lakesoul_amd.ops import cpp, hip
 
     n = 50000
-    rng = np.random.default_rng(2)
-    cat = (rng.integers(0, 100, n) * 7).astype(np.int64)
-    conv = float if stored == "float64" else int
-    vals = [None if rng.random() < 0.1 else conv(cat[i]) for i in range(n)]
-    pa_type = {"int64": pa.int64(), "int32": pa.int32(),
-               "float64": pa.float64()}[stored]
-    tbl = pa.table({"a": pa.array(np.arange(n, dtype=np.int64)),
-                    "c": pa.array(vals, type=pa_type)})
     path = tmp_path / "dict.parquet"
-    pq.write_table(tbl, str(path), use_dictionary=["c"], compression="zstd",
-                   row_group_size=20000)
-    assert pq.ParquetFile(str(path)).metadata.num_row_groups == 3
+    want, valid = _write_dict_file(path, stored, card, n)
 
     raw = cpp().read_unit_raw([str(path)], ["a", "c"], 0, False)
     tr = UnitTransfer(raw, dev)
@@ -156,11 +298,8 @@ def test_rle_dict_decode_gpu_vs_pyarrow(dev, tmp_path, stored):
     got = c_bytes.view(getattr(torch, stored)).cpu().numpy()
     mask = c_valid.cpu().numpy()
     assert len(got) == n and len(mask) == n
-    for i in range(n):
-        if vals[i] is None:
-            assert mask[i] == 0
-        else:
-            assert mask[i] == 1 and got[i] == vals[i]
+    np.testing.assert_array_equal(mask, valid.astype(np.uint8))
+    np.testing.assert_array_equal(got[valid], want[valid])
 
 
 def test_gather_strings_kernel(dev):
