@@ -586,13 +586,15 @@ static py::list read_chunks_raw_batch(int64_t h,
 static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
                                  const std::vector<std::string>& names,
                                  int64_t nthreads, bool pin, bool gpu_snappy,
-                                 bool gpu_zstd, double gpu_zstd_frac) {
+                                 bool gpu_zstd, double gpu_zstd_frac,
+                                 bool gpu_delta) {
   (void)nthreads;
   std::unique_ptr<UnitStage> st;
   auto t0 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
-    st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac);
+    st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac,
+                          gpu_delta);
   }
   auto t1 = std::chrono::steady_clock::now();
   UnitStage& ud = *st;
@@ -614,6 +616,9 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   torch::Tensor runs = torch::empty({(int64_t)ud.runs.size()}, torch::kInt64);
   if (!ud.runs.empty())
     std::memcpy(runs.data_ptr(), ud.runs.data(), ud.runs.size() * 8);
+  torch::Tensor enc = torch::empty({(int64_t)ud.enc.size()}, torch::kInt64);
+  if (!ud.enc.empty())
+    std::memcpy(enc.data_ptr(), ud.enc.data(), ud.enc.size() * 8);
   torch::Tensor sjobs = torch::empty({(int64_t)ud.snappy_jobs.size()}, torch::kInt64);
   if (!ud.snappy_jobs.empty())
     std::memcpy(sjobs.data_ptr(), ud.snappy_jobs.data(), ud.snappy_jobs.size() * 8);
@@ -643,6 +648,7 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   d["dicts"] = dicts;
   d["runs"] = runs;
   d["soffs"] = soffs;
+  d["enc"] = enc;
   d["comp"] = comp;
   d["snappy_jobs"] = sjobs;
   d["zstd_jobs"] = zjobs;
@@ -673,6 +679,10 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
     da[i][UD_SOFF_OFF] = c.soff_off;
     da[i][UD_SBYTES_OFF] = c.sbytes_off;
     da[i][UD_SBYTES_LEN] = c.sbytes_len;
+    da[i][UD_ENC] = c.enc;
+    da[i][UD_ENC_OFF] = c.enc_off;
+    da[i][UD_ENC_CNT] = c.enc_cnt;
+    da[i][UD_ENC_PAGES] = c.enc_pages;
   }
   d["desc"] = dt;
   // free the staging structures (dozens of MB of chunk vectors) off the
@@ -877,9 +887,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("read_unit_raw", &read_unit_raw_py, py::arg("paths"), py::arg("names"),
         py::arg("nthreads") = 0, py::arg("pin") = true,
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
-        py::arg("gpu_zstd_frac") = 1.0);
+        py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false);
   // the one descriptor column python looks at (fast-path eligibility)
   m.attr("UD_PRESENT") = (int)UD_PRESENT;
+  // where a column's regions lie, and its GPU-decoded value encoding
+  // (tests read both off the descriptor)
+  m.attr("UD_NUM_VALUES") = (int)UD_NUM_VALUES;
+  m.attr("UD_NULL_COUNT") = (int)UD_NULL_COUNT;
+  m.attr("UD_VAL_OFF") = (int)UD_VAL_OFF;
+  m.attr("UD_VAL_LEN") = (int)UD_VAL_LEN;
+  m.attr("UD_VALIDITY_OFF") = (int)UD_VALIDITY_OFF;
+  m.attr("UD_SOFF_OFF") = (int)UD_SOFF_OFF;
+  m.attr("UD_SBYTES_OFF") = (int)UD_SBYTES_OFF;
+  m.attr("UD_SBYTES_LEN") = (int)UD_SBYTES_LEN;
+  m.attr("UD_ENC") = (int)UD_ENC;
+  m.attr("UD_ENC_OFF") = (int)UD_ENC_OFF;
+  m.attr("UD_ENC_CNT") = (int)UD_ENC_CNT;
+  m.attr("UD_ENC_PAGES") = (int)UD_ENC_PAGES;
+  m.attr("UD_ENC_DELTA_BINARY") = (int)ParquetFile::ENCK_DELTA_BINARY;
+  m.attr("UD_ENC_BYTE_STREAM_SPLIT") = (int)ParquetFile::ENCK_BYTE_STREAM_SPLIT;
   m.def("read_chunks_raw_batch", &read_chunks_raw_batch);
   m.def("zstd_compress_ref", [](py::bytes src, int64_t level) {
     std::string b = src;

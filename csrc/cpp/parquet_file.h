@@ -31,6 +31,7 @@
 #include <unordered_map>
 
 #include "compress.h"
+#include "delta.h"
 #include "parquet_types.h"
 #include "rle.h"
 
@@ -702,6 +703,15 @@ class ParquetFile {
     int32_t bit_width;
   };
 
+  // GPU-decoded value encodings (ChunkData::enc_kind)
+  enum EncKind : int32_t { ENCK_NONE = 0, ENCK_DELTA_BINARY = 1, ENCK_BYTE_STREAM_SPLIT = 2 };
+
+  struct EncPage {  // raw DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT page payload
+    int64_t n;            // stored (non-null) values in page
+    int64_t payload_off;  // offset into ChunkData.values (8-byte aligned)
+    int64_t payload_len;
+  };
+
   struct CompPage {  // GPU-decompress job (snappy/zstd, levels-free pages)
     int64_t comp_off;   // into comp buffer
     int64_t comp_len;
@@ -728,6 +738,11 @@ class ParquetFile {
     std::vector<uint8_t> dict;      // PLAIN dictionary payload
     int64_t dict_num_values = 0;
     std::vector<IdxPage> idx_pages;
+    // gpu_delta mode: every page of the chunk is DELTA_BINARY_PACKED or
+    // every page BYTE_STREAM_SPLIT; values holds the raw (decompressed)
+    // page payloads, enc_pages one entry per data page
+    int32_t enc_kind = ENCK_NONE;
+    std::vector<EncPage> enc_pages;
     // gpu_compressed mode: values stays EMPTY; `comp` holds the raw
     // snappy page bodies and `comp_pages` the decompress jobs; values
     // stream length is values_len (sum of uncompressed page payloads)
@@ -748,11 +763,58 @@ class ParquetFile {
 
   const uint8_t* data_at(int64_t off) const { return map_ + off; }
 
+  // Turn the dictionary index pages of a (non-list) chunk into PLAIN
+  // values: the chunk is a plain one afterwards. For a dictionary chunk
+  // whose later pages fall back to another encoding (parquet-mr: PLAIN or
+  // DELTA_* once the dictionary grows too large), and for a dictionary
+  // chunk next to plain chunks of the same column.
+  static void undict_chunk(ChunkData& ch) {
+    std::vector<uint8_t> plain;
+    const bool is_bytes = ch.physical == PT_BYTE_ARRAY;
+    const size_t es = is_bytes ? 0 : (size_t)physical_elem_size(ch.physical);
+    std::vector<size_t> entry;  // byte arrays: where each (len, bytes) starts
+    if (is_bytes) {
+      size_t pos = 0;
+      for (int64_t i = 0; i < ch.dict_num_values; i++) {
+        uint32_t len;
+        if (pos + 4 > ch.dict.size()) throw std::runtime_error("dictionary page too short");
+        std::memcpy(&len, ch.dict.data() + pos, 4);
+        if (len > ch.dict.size() - pos - 4) throw std::runtime_error("dictionary page too short");
+        entry.push_back(pos);
+        pos += 4 + (size_t)len;
+      }
+      entry.push_back(pos);
+    } else if ((size_t)ch.dict_num_values * es > ch.dict.size()) {
+      throw std::runtime_error("dictionary page too short");
+    }
+    std::vector<int32_t> idx;
+    for (auto& ip : ch.idx_pages) {
+      idx.assign((size_t)ip.n, 0);
+      rle_decode<int32_t>(ch.values.data() + ip.payload_off,
+                          (size_t)ip.payload_len, ip.bit_width, ip.n, idx.data());
+      for (int32_t k : idx) {
+        if (k < 0 || k >= ch.dict_num_values)
+          throw std::runtime_error("dictionary index out of range");
+        const uint8_t* src = ch.dict.data() + (is_bytes ? entry[k] : (size_t)k * es);
+        size_t len = is_bytes ? entry[k + 1] - entry[k] : es;
+        plain.insert(plain.end(), src, src + len);
+      }
+    }
+    ch.values = std::move(plain);
+    ch.idx_pages.clear();
+    ch.is_dict = false;
+  }
+
   // gpu_snappy / gpu_zstd: defer page decompression to the GPU kernels
   // when the column is REQUIRED (no def-level section inside the
   // compressed blob), PLAIN-encoded, non-boolean v1 pages.
+  // gpu_delta: keep DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT page payloads
+  // raw for the GPU kernels (csrc/hip/delta.hip) when every page of the
+  // chunk has that one encoding and there is no dictionary page; any
+  // other chunk decodes on the host as without the flag.
   ChunkData read_chunk(size_t rg, size_t col, bool gpu_snappy = false,
-                       bool defer_host = false, bool gpu_zstd = false) const {
+                       bool defer_host = false, bool gpu_zstd = false,
+                       bool gpu_delta = false) const {
     // descriptor cache: lakehouse files are immutable, and deferred /
     // gpu-staged chunks are pure page descriptors (no payload) — cache
     // them so repeated scans skip the per-page thrift header walk
@@ -766,7 +828,7 @@ class ParquetFile {
       if (it != chunk_meta_cache_.end()) return *it->second;
     }
     ChunkData out_cached = read_chunk_impl(rg, col, gpu_snappy, defer_host,
-                                           gpu_zstd);
+                                           gpu_zstd, gpu_delta);
     if ((out_cached.host_deferred || out_cached.gpu_compressed) &&
         out_cached.values.empty() && out_cached.validity.empty() &&
         out_cached.dict.empty() && out_cached.comp.empty()) {
@@ -779,7 +841,8 @@ class ParquetFile {
 
   ChunkData read_chunk_impl(size_t rg, size_t col, bool gpu_snappy = false,
                             bool defer_host = false,
-                            bool gpu_zstd = false) const {
+                            bool gpu_zstd = false,
+                            bool gpu_delta = false) const {
     const RowGroup& g = meta_.row_groups.at(rg);
     const ColumnMeta& cm = g.columns.at(col);
     const ColumnDesc& cd = cols_.at(col);
@@ -804,6 +867,7 @@ class ParquetFile {
     int64_t values_seen = 0;
     out.values.reserve((size_t)cm.total_uncompressed_size);
     bool any_null_page = false;
+    bool undicted = false;  // dictionary index pages were turned into values
     // validity allocated lazily on the first null (REQUIRED columns and
     // fully-valid chunks never pay the memset)
     auto ensure_validity = [&]() {
@@ -993,6 +1057,13 @@ class ParquetFile {
       out.null_count += page_nulls - page_markers;  // null ELEMENTS only
       int64_t nonnull = nv - page_nulls;            // stored values
 
+      const bool dict_page = ph.encoding == ENC_RLE_DICTIONARY ||
+                             ph.encoding == ENC_PLAIN_DICTIONARY;
+      if (out.is_dict && !dict_page && !cd.is_list) {
+        // fallback page in a dictionary chunk: plain from here on
+        undict_chunk(out);
+        undicted = true;
+      }
       if (ph.encoding == ENC_PLAIN) {
         if (cd.physical == PT_BOOLEAN) {
           // unpack bits to bytes here (cheap, host)
@@ -1007,8 +1078,10 @@ class ParquetFile {
         } else {
           out.values.insert(out.values.end(), vals, vals + vals_len);
         }
-      } else if (ph.encoding == ENC_RLE_DICTIONARY ||
-                 ph.encoding == ENC_PLAIN_DICTIONARY) {
+      } else if (dict_page) {
+        if (undicted)
+          throw std::runtime_error(
+              "unsupported: dictionary page after fallback pages");
         out.is_dict = true;
         int bw = vals[0];
         IdxPage ip;
@@ -1021,9 +1094,65 @@ class ParquetFile {
         ip.bit_width = bw;
         out.idx_pages.push_back(ip);
         out.values.insert(out.values.end(), vals + 1, vals + vals_len);
+      } else if (ph.encoding == ENC_DELTA_BINARY_PACKED ||
+                 ph.encoding == ENC_BYTE_STREAM_SPLIT ||
+                 ph.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY ||
+                 ph.encoding == ENC_DELTA_BYTE_ARRAY) {
+        if (cd.is_list)
+          throw std::runtime_error("LIST columns: data encoding " +
+                                   std::to_string(ph.encoding) +
+                                   " not supported");
+        bool fixed48 = cd.physical == PT_INT32 || cd.physical == PT_INT64 ||
+                       cd.physical == PT_FLOAT || cd.physical == PT_DOUBLE;
+        int32_t kind = ENCK_NONE;
+        if (ph.encoding == ENC_DELTA_BINARY_PACKED &&
+            (cd.physical == PT_INT32 || cd.physical == PT_INT64))
+          kind = ENCK_DELTA_BINARY;
+        else if (ph.encoding == ENC_BYTE_STREAM_SPLIT && fixed48)
+          kind = ENCK_BYTE_STREAM_SPLIT;
+        else if (!(cd.physical == PT_BYTE_ARRAY &&
+                   (ph.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY ||
+                    ph.encoding == ENC_DELTA_BYTE_ARRAY)))
+          throw std::runtime_error(
+              "unsupported data encoding " + std::to_string(ph.encoding) +
+              " for physical type " + std::to_string(cd.physical));
+        if (gpu_delta && kind != ENCK_NONE && out.dict.empty() &&
+            (out.enc_kind == kind ||
+             (out.enc_kind == ENCK_NONE && out.values.empty() &&
+              values_seen == 0))) {
+          out.enc_kind = kind;
+          EncPage ep;
+          out.values.resize((out.values.size() + 7) & ~(size_t)7, 0);
+          ep.n = nonnull;
+          ep.payload_off = (int64_t)out.values.size();
+          ep.payload_len = nonnull > 0 ? (int64_t)vals_len : 0;
+          if (nonnull > 0)
+            out.values.insert(out.values.end(), vals, vals + vals_len);
+          out.enc_pages.push_back(ep);
+        } else if (out.enc_kind != ENCK_NONE) {
+          // mixed encodings inside the chunk — redo on the host route
+          return read_chunk_impl(rg, col, false, false, false, false);
+        } else if (kind == ENCK_DELTA_BINARY) {
+          if (cd.physical == PT_INT32)
+            delta_binary_decode<int32_t>(vals, vals_len, nonnull, out.values);
+          else
+            delta_binary_decode<int64_t>(vals, vals_len, nonnull, out.values);
+        } else if (kind == ENCK_BYTE_STREAM_SPLIT) {
+          byte_stream_split_decode(vals, vals_len, nonnull,
+                                   physical_elem_size(cd.physical), out.values);
+        } else if (ph.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY) {
+          delta_length_byte_array_decode(vals, vals_len, nonnull, out.values);
+        } else {
+          delta_byte_array_decode(vals, vals_len, nonnull, out.values);
+        }
       } else {
         throw std::runtime_error("unsupported data encoding " +
                                  std::to_string(ph.encoding));
+      }
+      if (out.enc_kind != ENCK_NONE && ph.encoding != ENC_DELTA_BINARY_PACKED &&
+          ph.encoding != ENC_BYTE_STREAM_SPLIT) {
+        // a PLAIN / dictionary page after raw delta pages — redo on host
+        return read_chunk_impl(rg, col, false, false, false, false);
       }
       values_seen += nv;
     }

@@ -20,6 +20,22 @@
 //   runs    : int64 [m][6] {dense_out_off, n, is_literal,
 //             value_or_abs_bitoff, bit_width, dict_elem_bias}
 //   soffs   : int64 string offsets per (file,col), rebased across chunks
+//   enc     : int64 [m][6], GPU-decoded DELTA_BINARY_PACKED /
+//             BYTE_STREAM_SPLIT columns (gpu_delta; UD_ENC != 0). Their raw
+//             page payloads sit in values like dict-index payloads: each
+//             page 8-byte aligned, each chunk padded to 8, the region +8.
+//             Per (file,col): its page rows, then its miniblock rows.
+//               delta page : {dense_out_off, n, first_value,
+//                             first miniblock (index among the column's
+//                             miniblock rows), 0, 0}
+//               miniblock  : {dense_out_off of the first value it
+//                             produces, n, abs_bit_off into values,
+//                             bit_width, min_delta, page row}
+//               split page : {dense_out_off, n, abs_byte_off into values,
+//                             0, 0, 0}
+//             dense offsets count stored (non-null) values across the
+//             column's chunks. Every row comes from delta_walk (delta.h):
+//             its span is validated against the page before it is listed.
 #pragma once
 
 #include <atomic>
@@ -33,6 +49,7 @@
 
 #include <chrono>
 
+#include "delta.h"
 #include "parquet_file.h"
 #include "rle.h"
 #include "thread_pool.h"
@@ -102,6 +119,8 @@ struct UnitColumn {
   int64_t dict_off = 0, dict_len = 0;
   int64_t run_off = 0, run_cnt = 0;
   int64_t dense_n = 0;
+  int32_t enc = 0;  // ParquetFile::EncKind: raw pages, decoded on the GPU
+  int64_t enc_off = 0, enc_cnt = 0, enc_pages = 0;  // rows of UnitStage::enc
   int64_t soff_off = -1;
   int64_t sbytes_off = 0, sbytes_len = 0;
   bool is_list = false;  // element values in the sbytes region, element
@@ -128,6 +147,7 @@ struct UnitStage {
   std::vector<UnitColumn> cols;
   std::vector<int64_t> file_rows;
   std::vector<int64_t> runs;  // [m][6]
+  std::vector<int64_t> enc;   // [m][6], see the layout comment
   std::vector<int64_t> snappy_jobs;  // [m][4]: comp_off, comp_len, dst_off(values), dst_len
   std::vector<int64_t> zstd_jobs;    // [m][4]: same layout, zstd frames
   struct HostJob {
@@ -144,7 +164,7 @@ struct UnitStage {
 inline std::unique_ptr<UnitStage> read_unit_stage1(
     const std::vector<std::string>& paths, const std::vector<std::string>& names,
     bool gpu_snappy = false, bool gpu_zstd = false,
-    double gpu_zstd_frac = 1.0) {
+    double gpu_zstd_frac = 1.0, bool gpu_delta = false) {
   auto st = std::make_unique<UnitStage>();
   UnitStage& S = *st;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -193,13 +213,50 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         bool this_gpu_zstd =
             gpu_zstd && ((double)((i * 2654435761u) % 1000) < gpu_zstd_frac * 1000.0);
         fd.chunks[t.c][t.rg] =
-            fd.f->read_chunk(t.rg, fd.col_idx[t.c], gpu_snappy, true, this_gpu_zstd);
+            fd.f->read_chunk(t.rg, fd.col_idx[t.c], gpu_snappy, true, this_gpu_zstd,
+                             gpu_delta);
       } catch (std::exception& e) {
         std::lock_guard<std::mutex> lk(err_mu);
         err = e.what();
       }
     });
     if (!err.empty()) throw std::runtime_error(err);
+  }
+  // the GPU decode route holds per (file, column): all of its chunks raw
+  // in ONE encoding. Mixed encodings across row groups: host-decode the
+  // raw chunks, and the column is a plain one.
+  if (gpu_delta) {
+    for (auto& fd : S.files) {
+      for (size_t c = 0; c < names.size(); c++) {
+        auto& chs = fd.chunks[c];
+        if (chs.empty()) continue;  // the file lacks the column
+        bool any = false, uniform = true;
+        for (auto& ch : chs) {
+          if (ch.enc_kind) any = true;
+          if (ch.enc_kind != chs[0].enc_kind) uniform = false;
+        }
+        if (!any || uniform) continue;
+        for (size_t rg = 0; rg < chs.size(); rg++)
+          if (chs[rg].enc_kind)
+            chs[rg] = fd.f->read_chunk(rg, fd.col_idx[c], false, false, false, false);
+      }
+    }
+  }
+  // likewise a column is dictionary-decoded only when all of its chunks
+  // are: next to a plain chunk (a row group that fell back, or was
+  // host-decoded above) the dictionary chunks turn plain on the host
+  for (auto& fd : S.files) {
+    for (size_t c = 0; c < names.size(); c++) {
+      if (fd.col_idx[c] < 0 || fd.f->columns()[fd.col_idx[c]].is_list) continue;
+      bool any_dict = false, any_plain = false;
+      for (auto& ch : fd.chunks[c]) {
+        if (ch.is_dict) any_dict = true;
+        else if (ch.num_values > ch.null_count) any_plain = true;
+      }
+      if (!(any_dict && any_plain)) continue;
+      for (auto& ch : fd.chunks[c])
+        if (ch.is_dict) ParquetFile::undict_chunk(ch);
+    }
   }
   auto tp2 = now();
   S.t_open_us = us(tp0, tp1);
@@ -266,7 +323,57 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         uc.validity_off = vapos;
         vapos += nv;
       }
-      if (uc.is_string) {
+      if (!chs.empty() && chs[0].enc_kind) {
+        // raw DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages (every chunk,
+        // same kind: see the fix-up above): page and miniblock rows
+        uc.enc = chs[0].enc_kind;
+        uc.val_off = vpos;
+        int es = physical_elem_size(uc.physical);
+        std::vector<int64_t> pages, mbs;
+        int64_t poff = uc.val_off, dense_off = 0;
+        for (auto& ch : chs) {
+          for (auto& ep : ch.enc_pages) {
+            int64_t abs_off = poff + ep.payload_off;
+            int64_t page_row = (int64_t)pages.size() / 6;
+            if (uc.enc == ParquetFile::ENCK_BYTE_STREAM_SPLIT) {
+              if (ep.n > 0 && ep.n > ep.payload_len / es)
+                throw std::runtime_error(
+                    "byte-stream-split: page shorter than its values");
+              pages.insert(pages.end(), {dense_off, ep.n, abs_off, 0, 0, 0});
+            } else {
+              DeltaHeader h;
+              int64_t first_mb = (int64_t)mbs.size() / 6;
+              int64_t carried = 0;
+              if (ep.n > 0) {
+                delta_walk(ch.values.data() + ep.payload_off,
+                           (size_t)ep.payload_len, es * 8, (uint64_t)ep.n, h,
+                           [&](const DeltaMiniblock& m) {
+                  mbs.insert(mbs.end(),
+                             {dense_off + m.first, m.n, abs_off * 8 + m.bit_off,
+                              (int64_t)m.bit_width, (int64_t)m.min_delta,
+                              page_row});
+                  carried += m.n;
+                });
+                if ((int64_t)h.count != ep.n || carried + 1 != ep.n)
+                  throw std::runtime_error(
+                      "delta: stream holds fewer values than the page");
+              }
+              pages.insert(pages.end(), {dense_off, ep.n,
+                                         (int64_t)h.first_value, first_mb, 0, 0});
+            }
+            dense_off += ep.n;
+          }
+          poff += ru_align8((int64_t)ch.values.size());
+        }
+        uc.val_len = poff - uc.val_off + 8;
+        vpos += uc.val_len;
+        uc.dense_n = dense_off;
+        uc.enc_off = (int64_t)S.enc.size() / 6;
+        uc.enc_pages = (int64_t)pages.size() / 6;
+        S.enc.insert(S.enc.end(), pages.begin(), pages.end());
+        S.enc.insert(S.enc.end(), mbs.begin(), mbs.end());
+        uc.enc_cnt = (int64_t)S.enc.size() / 6 - uc.enc_off;
+      } else if (uc.is_string) {
         uc.soff_off = spos;
         spos += nv + 1;
       } else if (uc.is_dict) {
@@ -447,6 +554,15 @@ inline void read_unit_fill(UnitStage& S, uint8_t* values, uint8_t* validity,
       if (uc.is_list && uc.validity_off >= 0 && !sd.row_valid.empty())
         std::memcpy(validity + uc.validity_off, sd.row_valid.data(),
                     sd.row_valid.size());
+      return;
+    }
+    if (uc.enc) {
+      int64_t poff = uc.val_off;
+      for (auto& ch : chs) {
+        if (!ch.values.empty())
+          std::memcpy(values + poff, ch.values.data(), ch.values.size());
+        poff += ru_align8((int64_t)ch.values.size());
+      }
       return;
     }
     if (uc.is_dict) {

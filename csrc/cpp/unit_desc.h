@@ -22,5 +22,11 @@ enum UnitDescField {
   UD_SOFF_OFF,
   UD_SBYTES_OFF,
   UD_SBYTES_LEN,
+  // raw value pages decoded on the GPU (read_unit.h, `enc` table):
+  // 0 = none, 1 = DELTA_BINARY_PACKED, 2 = BYTE_STREAM_SPLIT
+  UD_ENC,
+  UD_ENC_OFF,    // first row of the column in the enc table
+  UD_ENC_CNT,    // its rows: page rows, then miniblock rows
+  UD_ENC_PAGES,  // how many of them are page rows
   UD_NFIELDS
 };

@@ -369,8 +369,9 @@ static std::vector<UnitCol> decode_unit_cols(
     const torch::Tensor& vals, const torch::Tensor& validity_buf,
     const torch::Tensor& dicts, const torch::Tensor& runs,
     const torch::Tensor& soffs, const torch::Tensor& desc, int64_t nfiles,
-    int64_t ncols) {
+    int64_t ncols, const torch::Tensor& enc) {
   CHECK_GPU_NONEMPTY(validity_buf);
+  CHECK_GPU_NONEMPTY(enc);
   CHECK_GPU_NONEMPTY(dicts);
   CHECK_GPU_NONEMPTY(runs);
   CHECK_GPU_NONEMPTY(soffs);
@@ -383,6 +384,10 @@ static std::vector<UnitCol> decode_unit_cols(
   auto da = desc.accessor<int64_t, 2>();
   auto stream = cur_stream();
   torch::Tensor runs2 = runs.numel() ? runs.view({-1, 6}) : runs;
+  TORCH_CHECK(enc.numel() == 0 ||
+                  (enc.scalar_type() == torch::kInt64 && enc.numel() % 6 == 0),
+              "decode_unit: enc must be an int64 [m, 6] tensor");
+  const int64_t enc_rows = enc.numel() / 6;
 
   std::vector<UnitCol> cols((size_t)(nfiles * ncols));
   for (int64_t u = 0; u < nfiles * ncols; u++) {
@@ -402,7 +407,57 @@ static std::vector<UnitCol> decode_unit_cols(
       continue;
     }
     int64_t es = d[UD_ESIZE];
-    if (d[UD_IS_DICT]) {
+    if (d[UD_ENC]) {
+      // raw DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages -> the DENSE
+      // column (delta.hip); nulls then scatter like a PLAIN column
+      int64_t np = d[UD_ENC_PAGES], nm = d[UD_ENC_CNT] - np, dn = d[UD_DENSE_N];
+      TORCH_CHECK(es == 4 || es == 8, "decode_unit: encoded column of elem size ", es);
+      TORCH_CHECK(np >= 0 && nm >= 0 && d[UD_ENC_OFF] >= 0 &&
+                      d[UD_ENC_OFF] + d[UD_ENC_CNT] <= enc_rows,
+                  "decode_unit: enc rows out of range (was the enc table passed?)");
+      TORCH_CHECK(d[UD_VAL_OFF] >= 0 && d[UD_VAL_OFF] + d[UD_VAL_LEN] <= vals.numel(),
+                  "decode_unit: encoded payload out of range");
+      TORCH_CHECK(dn >= 0 && dn <= nv, "decode_unit: bad dense count");
+      const int64_t* pages = enc.data_ptr<int64_t>() + d[UD_ENC_OFF] * 6;
+      const int64_t* mbs = pages + np * 6;
+      // payload reads are bounded by the END OF THIS COLUMN's region
+      const int64_t vend = d[UD_VAL_OFF] + d[UD_VAL_LEN];
+      auto dense = torch::empty({dn * es}, u8);
+      if (d[UD_ENC] == 1) {
+        TORCH_CHECK(nm == 0 || np > 0, "decode_unit: miniblocks without a page");
+        torch::Tensor totals, csum;
+        const int64_t *tp = nullptr, *cp = nullptr;
+        if (nm) {
+          totals = torch::empty({nm}, u8.dtype(torch::kInt64));
+          if (es == 4)
+            launch_delta_binary_pass1<uint32_t>(vals.data_ptr<uint8_t>(), vend, mbs, nm, (uint32_t*)dense.data_ptr(), dn, totals.data_ptr<int64_t>(), stream);
+          else
+            launch_delta_binary_pass1<uint64_t>(vals.data_ptr<uint8_t>(), vend, mbs, nm, (uint64_t*)dense.data_ptr(), dn, totals.data_ptr<int64_t>(), stream);
+          csum = at::cumsum(totals, 0);
+          tp = totals.data_ptr<int64_t>();
+          cp = csum.data_ptr<int64_t>();
+        }
+        if (es == 4)
+          launch_delta_binary_pass2<uint32_t>(pages, np, mbs, nm, tp, cp, (uint32_t*)dense.data_ptr(), dn, stream);
+        else
+          launch_delta_binary_pass2<uint64_t>(pages, np, mbs, nm, tp, cp, (uint64_t*)dense.data_ptr(), dn, stream);
+      } else {
+        TORCH_CHECK(d[UD_ENC] == 2 && nm == 0, "decode_unit: unknown encoding tag ", d[UD_ENC]);
+        if (es == 4)
+          launch_byte_stream_split<uint32_t>(vals.data_ptr<uint8_t>(), vend, pages, np, (uint32_t*)dense.data_ptr(), dn, stream);
+        else
+          launch_byte_stream_split<uint64_t>(vals.data_ptr<uint8_t>(), vend, pages, np, (uint64_t*)dense.data_ptr(), dn, stream);
+      }
+      if (has_null) {
+        auto pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
+        out.data = torch::zeros({nv * es}, u8);
+        scatter_valid_es(es, dense.data_ptr(), vmask.data_ptr<uint8_t>(),
+                         pos.data_ptr<int64_t>(), out.data.data_ptr(), nv, stream);
+      } else {
+        TORCH_CHECK(dn == nv, "decode_unit: dense count differs from the row count");
+        out.data = dense;
+      }
+    } else if (d[UD_IS_DICT]) {
       auto rr = runs2.narrow(0, d[UD_RUN_OFF], d[UD_RUN_CNT]);
       // run bit offsets are relative to the whole values buffer (they
       // already include this chunk's val_off, see read_unit.h)
@@ -434,6 +489,12 @@ static std::vector<UnitCol> decode_unit_cols(
   return cols;
 }
 
+// the enc table is a trailing, optional argument of the unit bindings:
+// units without GPU-decoded encodings never pass it
+static torch::Tensor enc_or_empty(const c10::optional<torch::Tensor>& enc) {
+  return enc.has_value() ? *enc : torch::empty({0}, torch::kInt64);
+}
+
 static py::object tensor_or_none(const torch::Tensor& t) {
   return t.defined() ? py::cast(t) : py::none();
 }
@@ -458,12 +519,13 @@ static py::list unit_cols_to_py(const std::vector<UnitCol>& cols) {
 static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
                             torch::Tensor dicts, torch::Tensor runs,
                             torch::Tensor soffs, torch::Tensor desc,
-                            int64_t nfiles, int64_t ncols) {
+                            int64_t nfiles, int64_t ncols,
+                            c10::optional<torch::Tensor> enc) {
   std::vector<UnitCol> cols;
   {
     py::gil_scoped_release rel;
     cols = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
-                            nfiles, ncols);
+                            nfiles, ncols, enc_or_empty(enc));
   }
   return unit_cols_to_py(cols);
 }
@@ -524,11 +586,11 @@ static std::vector<UnitCol> scan_unit_uselast_cols(
     const torch::Tensor& vals, const torch::Tensor& validity_buf,
     const torch::Tensor& dicts, const torch::Tensor& runs,
     const torch::Tensor& soffs, const torch::Tensor& desc, int64_t nfiles,
-    int64_t ncols, int64_t pk_ci, int64_t pk_es) {
+    int64_t ncols, int64_t pk_ci, int64_t pk_es, const torch::Tensor& enc) {
   TORCH_CHECK(nfiles >= 1 && pk_ci >= 0 && pk_ci < ncols && (pk_es == 4 || pk_es == 8),
               "scan_unit_uselast: bad pk column");
   auto flat = decode_unit_cols(vals, validity_buf, dicts, runs, soffs, desc,
-                               nfiles, ncols);
+                               nfiles, ncols, enc);
   for (auto& c : flat)
     TORCH_CHECK(c.present && !c.is_list,
                 "scan_unit_uselast: absent or list column (fallback)");
@@ -574,12 +636,13 @@ static py::list scan_unit_uselast(torch::Tensor vals, torch::Tensor validity_buf
                                   torch::Tensor dicts, torch::Tensor runs,
                                   torch::Tensor soffs, torch::Tensor desc,
                                   int64_t nfiles, int64_t ncols, int64_t pk_ci,
-                                  int64_t pk_es) {
+                                  int64_t pk_es,
+                                  c10::optional<torch::Tensor> enc) {
   std::vector<UnitCol> cols;
   {
     py::gil_scoped_release rel;  // long device-side section
     cols = scan_unit_uselast_cols(vals, validity_buf, dicts, runs, soffs, desc,
-                                  nfiles, ncols, pk_ci, pk_es);
+                                  nfiles, ncols, pk_ci, pk_es, enc_or_empty(enc));
   }
   return unit_cols_to_py(cols);
 }
@@ -723,8 +786,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("snappy_decompress", &snappy_decompress);
   m.def("snappy_decompress_into", &snappy_decompress_into);
-  m.def("scan_unit_uselast", &scan_unit_uselast);
-  m.def("decode_unit", &decode_unit);
+  m.def("scan_unit_uselast", &scan_unit_uselast, py::arg("vals"),
+        py::arg("validity"), py::arg("dicts"), py::arg("runs"), py::arg("soffs"),
+        py::arg("desc"), py::arg("nfiles"), py::arg("ncols"), py::arg("pk_ci"),
+        py::arg("pk_es"), py::arg("enc") = py::none());
+  m.def("decode_unit", &decode_unit, py::arg("vals"), py::arg("validity"),
+        py::arg("dicts"), py::arg("runs"), py::arg("soffs"), py::arg("desc"),
+        py::arg("nfiles"), py::arg("ncols"), py::arg("enc") = py::none());
   m.doc() = "lakesoul_amd gfx950 HIP kernels";
   m.def("hash_fixed_column", &hash_fixed_column);
   m.def("hash_string_column", &hash_string_column);

@@ -93,6 +93,23 @@ void launch_fastscan_ex_dot_pairs(const uint8_t* ex, const int64_t* cand,
                                   int32_t nq, int32_t wn, int32_t dim,
                                   hipStream_t s);
 
+// delta.hip — raw DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages; table
+// rows int64 [.][6] as laid out in ../cpp/read_unit.h (`enc`); T is
+// uint32_t or uint64_t; `out` holds dense_n values
+template <typename T>
+void launch_delta_binary_pass1(const uint8_t* payload, int64_t vals_len,
+                               const int64_t* mbs, int64_t nmb, T* out,
+                               int64_t dense_n, int64_t* totals, hipStream_t s);
+template <typename T>
+void launch_delta_binary_pass2(const int64_t* pages, int64_t npages,
+                               const int64_t* mbs, int64_t nmb,
+                               const int64_t* totals, const int64_t* csum, T* out,
+                               int64_t dense_n, hipStream_t s);
+template <typename T>
+void launch_byte_stream_split(const uint8_t* payload, int64_t vals_len,
+                              const int64_t* pages, int64_t npages, T* out,
+                              int64_t dense_n, hipStream_t s);
+
 // snappy.hip, zstd.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,

@@ -5,11 +5,12 @@ Pipeline per scan unit:
    zstd/snappy decompress, def-level RLE decode, and layout of every
    chunk payload into a handful of contiguous (pinned) buffers
    (_cpp.read_unit_raw / csrc/cpp/read_unit.h);
-2. ONE async H2D per buffer (values / validity / dicts / runs);
+2. ONE async H2D per buffer (values / validity / dicts / runs / enc);
 3. HIP kernels materialize columns in HBM: PLAIN fixed-width columns are
    zero-copy views into the device buffer; dictionary chunks expand with
-   the RLE bit-unpack kernel + fused dict-gather/null-scatter; nullable
-   PLAIN columns scatter through validity;
+   the RLE bit-unpack kernel + fused dict-gather/null-scatter; raw
+   DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages decode with the delta.hip
+   kernels; nullable PLAIN columns scatter through validity;
 4. GPU merge-on-read (merge_gpu) with the merge-path kernel.
 
 String columns are host-assembled ((len,bytes) stream is serial) and ship
@@ -79,13 +80,22 @@ def _default_gpu_zstd_frac() -> float:
 _GPU_ZSTD_FRAC = _default_gpu_zstd_frac()
 _GPU_ZSTD = _GPU_ZSTD_FRAC > 0.0
 
+# DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages of foreign files: ship the
+# raw pages and decode them in HBM (csrc/hip/delta.hip) unless
+# LAKESOUL_GPU_DELTA=0 forces the host decode. The default rests on bus
+# volume (a delta-packed sorted int64 key is a few bits per row against
+# 8 B/row host-decoded) and on one micro-benchmark of single-column unit
+# reads (benchmarks/delta_micro.py, profiles/delta_micro.md: GPU route
+# 1.4x-7x the host route); no scan-level A/B has been measured.
+_GPU_DELTA = _os.environ.get("LAKESOUL_GPU_DELTA", "1") != "0"
+
 
 def fetch_raw(files: List[str], names: List[str]) -> dict:
     """Host phase of a unit read (releases the GIL in C++) — safe to run
     on a prefetch thread while the GPU processes the previous unit."""
     with timing.phase("host_fetch"):
         raw = cpp().read_unit_raw(files, names, 0, True, True, _GPU_ZSTD,
-                                  _GPU_ZSTD_FRAC)
+                                  _GPU_ZSTD_FRAC, _GPU_DELTA)
     if timing.ENABLED:
         timing._acc["fetch.stage1"] += raw["t_stage1_us"] / 1e6
         timing._acc["fetch.s1_open"] += raw["t_open_us"] / 1e6
@@ -140,6 +150,10 @@ class UnitTransfer:
             if raw["runs"].numel() else None
         )
         self.soffs = raw["soffs"].to(device, non_blocking=True) if raw["soffs"].numel() else None
+        self.enc = (
+            raw["enc"].view(-1, 6).to(device, non_blocking=True)
+            if raw.get("enc") is not None and raw["enc"].numel() else None
+        )
         self.comp = raw["comp"].to(device, non_blocking=True) if raw.get("comp") is not None and raw["comp"].numel() else None
         self.snappy_jobs = (
             raw["snappy_jobs"].view(-1, 4).to(device, non_blocking=True)
@@ -250,7 +264,8 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
         with timing.phase("gpu_unit_cpp", sync_gpu=False):
             pk_ci = names.index(scan.pk[0])
             pk_es = 8 if scan.schema.field(scan.pk[0]).dtype == "int64" else 4
-            outs = hip().scan_unit_uselast(*unit_bufs, pk_ci, pk_es)
+            outs = hip().scan_unit_uselast(*unit_bufs, pk_ci, pk_es,
+                                           transfer.enc)
         merged = {f.name: _wrap_column(f, outs[ci])
                   for ci, f in enumerate(fields)}
         return scan._to_eval_batch(merged, unit, len(merged[names[0]]), device)
@@ -259,7 +274,7 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
     file_batches: List[Batch] = []
     present: List[set] = []
     with timing.phase("gpu_decode", sync_gpu=True):
-        outs = hip().decode_unit(*unit_bufs)
+        outs = hip().decode_unit(*unit_bufs, transfer.enc)
         for fi, nrows in enumerate(raw["file_rows"]):
             cols: Dict[str, Column] = {}
             pres = set()
