@@ -15,6 +15,7 @@
 #include "parquet_file.h"
 #include "read_unit.h"
 #include "unit_desc.h"
+#include "huf_par.h"
 #include "zstd_dec.h"
 
 namespace py = pybind11;
@@ -587,14 +588,14 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
                                  const std::vector<std::string>& names,
                                  int64_t nthreads, bool pin, bool gpu_snappy,
                                  bool gpu_zstd, double gpu_zstd_frac,
-                                 bool gpu_delta) {
+                                 bool gpu_delta, bool gpu_huf) {
   (void)nthreads;
   std::unique_ptr<UnitStage> st;
   auto t0 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
     st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac,
-                          gpu_delta);
+                          gpu_delta, gpu_huf);
   }
   auto t1 = std::chrono::steady_clock::now();
   UnitStage& ud = *st;
@@ -625,6 +626,9 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   torch::Tensor zjobs = torch::empty({(int64_t)ud.zstd_jobs.size()}, torch::kInt64);
   if (!ud.zstd_jobs.empty())
     std::memcpy(zjobs.data_ptr(), ud.zstd_jobs.data(), ud.zstd_jobs.size() * 8);
+  torch::Tensor hjobs = torch::empty({(int64_t)ud.huf_jobs.size()}, torch::kInt64);
+  if (!ud.huf_jobs.empty())
+    std::memcpy(hjobs.data_ptr(), ud.huf_jobs.data(), ud.huf_jobs.size() * 8);
   auto t2 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
@@ -652,6 +656,7 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   d["comp"] = comp;
   d["snappy_jobs"] = sjobs;
   d["zstd_jobs"] = zjobs;
+  d["huf_jobs"] = hjobs;
   py::list frows;
   for (auto r : ud.file_rows) frows.append(r);
   d["file_rows"] = frows;
@@ -887,7 +892,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("read_unit_raw", &read_unit_raw_py, py::arg("paths"), py::arg("names"),
         py::arg("nthreads") = 0, py::arg("pin") = true,
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
-        py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false);
+        py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false,
+        py::arg("gpu_huf") = false);
   // the one descriptor column python looks at (fast-path eligibility)
   m.attr("UD_PRESENT") = (int)UD_PRESENT;
   // where a column's regions lie, and its GPU-decoded value encoding
@@ -978,6 +984,47 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }
     return count;
   });
+  m.def("zstd_huf_only", [](py::bytes bytes, int64_t rs) {
+    // the page classifier of the GPU Huffman route: is `bytes` a
+    // Huffman-only page of rs bytes?
+    std::string b = bytes;
+    lszstd::HufOnly ho;
+    const uint8_t* src = (const uint8_t*)b.data();
+    return lszstd::huf_only_frame(src, (int64_t)b.size(), rs, ho);
+  }, py::arg("frame"), py::arg("rs"));
+  m.def("zstd_huf_census", [](py::bytes bytes, int64_t rs) {
+    // of an accepted frame: streams, literals size format, the table's
+    // maxBits and whether the tree description is direct or FSE-compressed
+    std::string b = bytes;
+    const uint8_t* src = (const uint8_t*)b.data();
+    lszstd::HufOnly ho;
+    if (!lszstd::huf_only_frame(src, (int64_t)b.size(), rs, ho))
+      throw std::runtime_error("zstd_huf_census: not a Huffman-only frame");
+    auto c = std::make_unique<lszstd::HufParCtx>();
+    if (lszstd::read_huf_tree(src + ho.payload, ho.cs, c->huf, c->ws) < 0)
+      throw std::runtime_error("zstd_huf_census: bad tree description");
+    py::dict d;
+    d["streams"] = ho.nStreams;
+    d["size_format"] = ho.sizeFormat;
+    d["rs"] = ho.rs;
+    d["max_bits"] = c->huf.maxBits;
+    d["tree"] = lszstd::huf_desc_direct(src[ho.payload]) ? "direct" : "fse";
+    return d;
+  });
+  m.def("zstd_huf_par_decode_ref", [](py::bytes bytes, int64_t lanes, int64_t rs) {
+    // host twin of the GPU Huffman kernel (csrc/cpp/huf_par.h). Returns
+    // (bytes, fix-up rounds), or (None, rounds) where the decode fails;
+    // the destination is exactly rs bytes on the heap.
+    std::string b = bytes;
+    const uint8_t* src = (const uint8_t*)b.data();
+    if (rs < 0) throw std::runtime_error("zstd_huf_par_decode_ref: rs < 0");
+    auto c = std::make_unique<lszstd::HufParCtx>();
+    std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)rs]);
+    bool ok = lszstd::huf_par_decode(src, (int64_t)b.size(), out.get(), rs,
+                                     (int)lanes, *c);
+    if (!ok) return py::make_tuple(py::none(), c->rounds);
+    return py::make_tuple(py::bytes((const char*)out.get(), (size_t)rs), c->rounds);
+  }, py::arg("frame"), py::arg("lanes"), py::arg("rs"));
   m.def("hash_columns_cpu", &hash_columns_cpu);
   m.def("hash_string_column_cpu", &hash_string_column_cpu);
   m.def("bucket_ids_from_hashes", &bucket_ids_from_hashes);

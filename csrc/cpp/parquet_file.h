@@ -34,6 +34,7 @@
 #include "delta.h"
 #include "parquet_types.h"
 #include "rle.h"
+#include "zstd_dec.h"
 
 namespace lakesoul {
 
@@ -754,6 +755,10 @@ class ParquetFile {
     // later directly into the final buffer (no staging copy)
     bool host_deferred = false;
     std::vector<DeferPage> defer_pages;
+    // gpu_huf mode: the Huffman-only zstd pages of a host_deferred or
+    // gpu_compressed chunk (lszstd::huf_only_frame), by file offset like
+    // defer_pages: the GPU decodes them (csrc/hip/zstd_huf.hip)
+    std::vector<DeferPage> huf_pages;
     // LIST columns: rows -> element ranges (+1 sentinel) and per-row
     // validity; values/validity above then describe the ELEMENTS
     bool is_list = false;
@@ -812,23 +817,27 @@ class ParquetFile {
   // raw for the GPU kernels (csrc/hip/delta.hip) when every page of the
   // chunk has that one encoding and there is no dictionary page; any
   // other chunk decodes on the host as without the flag.
+  // gpu_huf (with defer_host or gpu_zstd): decided per page. A zstd page
+  // that could be deferred and is Huffman-only goes to huf_pages; the
+  // chunk's other pages follow the other flags as without it.
   ChunkData read_chunk(size_t rg, size_t col, bool gpu_snappy = false,
                        bool defer_host = false, bool gpu_zstd = false,
-                       bool gpu_delta = false) const {
+                       bool gpu_delta = false, bool gpu_huf = false) const {
+    gpu_huf = gpu_huf && (defer_host || gpu_zstd);
     // descriptor cache: lakehouse files are immutable, and deferred /
     // gpu-staged chunks are pure page descriptors (no payload) — cache
     // them so repeated scans skip the per-page thrift header walk
     // (reference analog: the global metadata cache, session.rs:86-105)
     uint64_t ckey = ((uint64_t)rg << 24) | ((uint64_t)col << 4) |
                     (defer_host ? 1u : 0u) | (gpu_snappy ? 2u : 0u) |
-                    (gpu_zstd ? 4u : 0u);
+                    (gpu_zstd ? 4u : 0u) | (gpu_huf ? 8u : 0u);
     if (defer_host || gpu_snappy || gpu_zstd) {
       std::lock_guard<std::mutex> lk(chunk_mu_);
       auto it = chunk_meta_cache_.find(ckey);
       if (it != chunk_meta_cache_.end()) return *it->second;
     }
     ChunkData out_cached = read_chunk_impl(rg, col, gpu_snappy, defer_host,
-                                           gpu_zstd, gpu_delta);
+                                           gpu_zstd, gpu_delta, gpu_huf);
     if ((out_cached.host_deferred || out_cached.gpu_compressed) &&
         out_cached.values.empty() && out_cached.validity.empty() &&
         out_cached.dict.empty() && out_cached.comp.empty()) {
@@ -842,7 +851,8 @@ class ParquetFile {
   ChunkData read_chunk_impl(size_t rg, size_t col, bool gpu_snappy = false,
                             bool defer_host = false,
                             bool gpu_zstd = false,
-                            bool gpu_delta = false) const {
+                            bool gpu_delta = false,
+                            bool gpu_huf = false) const {
     const RowGroup& g = meta_.row_groups.at(rg);
     const ColumnMeta& cm = g.columns.at(col);
     const ColumnDesc& cd = cols_.at(col);
@@ -905,6 +915,28 @@ class ParquetFile {
             ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN)) {
         // mixed chunk (dict fallback / oversized page) — redo on host
         return read_chunk_impl(rg, col, false);
+      }
+      lszstd::HufOnly ho;
+      if (gpu_huf && cm.codec == CODEC_ZSTD && ph.type == PAGE_DATA &&
+          ph.encoding == ENC_PLAIN && !cd.nullable &&
+          cd.physical != PT_BOOLEAN && cd.physical != PT_BYTE_ARRAY &&
+          cd.physical != PT_FLBA && cd.physical != PT_INT96 && !cd.is_list &&
+          out.dict.empty() && out.values.empty() &&
+          lszstd::huf_only_frame(body, ph.compressed_size,
+                                 ph.uncompressed_size, ho)) {
+        // the chunk's other pages go where they would without gpu_huf
+        if (!out.gpu_compressed && !out.host_deferred)
+          (gpu_zstd ? out.gpu_compressed : out.host_deferred) = true;
+        DeferPage dp;
+        dp.file_off = (int64_t)(body - map_);
+        dp.comp_len = ph.compressed_size;
+        dp.out_off = out.values_len;
+        dp.out_len = ph.uncompressed_size;
+        dp.codec = cm.codec;
+        out.huf_pages.push_back(dp);
+        out.values_len += ph.uncompressed_size;
+        values_seen += ph.num_values;
+        continue;
       }
       if (((gpu_snappy && cm.codec == CODEC_SNAPPY) ||
            (gpu_zstd && cm.codec == CODEC_ZSTD &&

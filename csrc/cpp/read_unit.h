@@ -156,6 +156,11 @@ struct UnitStage {
     int32_t codec;
   };
   std::vector<HostJob> host_jobs;
+  // Huffman-only zstd pages, decoded by zstd_huf.hip: jobs as zstd_jobs;
+  // huf_src[i] is where fill copies job i's frame from (HostJob with
+  // dst_off = its place in comp)
+  std::vector<int64_t> huf_jobs;
+  std::vector<HostJob> huf_src;
   std::vector<std::unique_ptr<StrDecoded>> str_cols;
   int64_t values_size = 0, validity_size = 0, dicts_size = 0, soffs_size = 0,
           comp_size = 0;
@@ -164,7 +169,7 @@ struct UnitStage {
 inline std::unique_ptr<UnitStage> read_unit_stage1(
     const std::vector<std::string>& paths, const std::vector<std::string>& names,
     bool gpu_snappy = false, bool gpu_zstd = false,
-    double gpu_zstd_frac = 1.0, bool gpu_delta = false) {
+    double gpu_zstd_frac = 1.0, bool gpu_delta = false, bool gpu_huf = false) {
   auto st = std::make_unique<UnitStage>();
   UnitStage& S = *st;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -214,7 +219,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
             gpu_zstd && ((double)((i * 2654435761u) % 1000) < gpu_zstd_frac * 1000.0);
         fd.chunks[t.c][t.rg] =
             fd.f->read_chunk(t.rg, fd.col_idx[t.c], gpu_snappy, true, this_gpu_zstd,
-                             gpu_delta);
+                             gpu_delta, gpu_huf);
       } catch (std::exception& e) {
         std::lock_guard<std::mutex> lk(err_mu);
         err = e.what();
@@ -264,6 +269,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
 
   // layout
   int64_t vpos = 0, vapos = 0, dpos = 0, spos = 0;
+  int64_t huf_comp = 0;  // bytes of Huffman-only frames so far
   for (size_t fi = 0; fi < nfiles; fi++) {
     auto& fd = S.files[fi];
     for (size_t c = 0; c < names.size(); c++) {
@@ -420,6 +426,16 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         uc.val_off = vpos;
         int64_t plen = 0;
         for (auto& ch : chs) {
+          // (huf_pages is empty unless the chunk is gpu_compressed or
+          // host_deferred; their frames follow everything else in comp)
+          for (auto& hp : ch.huf_pages) {
+            S.huf_jobs.insert(S.huf_jobs.end(),
+                              {huf_comp, hp.comp_len, vpos + plen + hp.out_off,
+                               hp.out_len});
+            S.huf_src.push_back(
+                {(int)fi, hp.file_off, hp.comp_len, huf_comp, hp.out_len, hp.codec});
+            huf_comp += hp.comp_len;
+          }
           if (ch.gpu_compressed) {
             for (auto& cp : ch.comp_pages) {
               auto& jobs = (cp.codec == CODEC_ZSTD) ? S.zstd_jobs : S.snappy_jobs;
@@ -505,6 +521,13 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     }
   }
 
+  // the Huffman-only frames go behind the chunk-owned page bodies in comp
+  for (size_t i = 0; i < S.huf_src.size(); i++) {
+    S.huf_jobs[4 * i] += S.comp_size;
+    S.huf_src[i].dst_off += S.comp_size;
+  }
+  S.comp_size += huf_comp;
+
   S.values_size = vpos;
   S.validity_size = vapos;
   S.dicts_size = dpos;
@@ -588,7 +611,19 @@ inline void read_unit_fill(UnitStage& S, uint8_t* values, uint8_t* validity,
   });
   // deferred pages: decompress straight from the file mmap into the
   // destination buffer (one pass, zero staging)
-  ThreadPool::instance().parallel_for((int64_t)S.host_jobs.size(), [&](int64_t i) {
+  // and, in the same sweep of the pool, the frames of the Huffman-only
+  // pages from the mmap into comp for the GPU (tens of MB per unit: not
+  // for the serial copy above)
+  const int64_t nhost = (int64_t)S.host_jobs.size();
+  const int64_t nhuf = comp ? (int64_t)S.huf_src.size() : 0;
+  ThreadPool::instance().parallel_for(nhost + nhuf, [&](int64_t i) {
+    if (i >= nhost) {
+      const UnitStage::HostJob& hs = S.huf_src[i - nhost];
+      std::memcpy(comp + hs.dst_off,
+                  S.files[hs.file_idx].f->data_at(hs.file_off),
+                  (size_t)hs.comp_len);
+      return;
+    }
     const UnitStage::HostJob& hj = S.host_jobs[i];
     const uint8_t* src = S.files[hj.file_idx].f->data_at(hj.file_off);
     decompress_into(hj.codec, values + hj.dst_off, (size_t)hj.dst_len, src,

@@ -142,6 +142,7 @@ struct BitFwd {
 // FSE
 // ---------------------------------------------------------------------- //
 
+static const int kHufMaxBits = 11;  // zstd huffman log limit
 static const int kMaxTableLog = 9;          // zstd: OF 8, ML 9, LL 9, weights 6
 static const int kMaxSymbols = 256;
 
@@ -167,6 +168,7 @@ struct BuildWs {
   uint16_t symNext[kMaxSymbols];
   uint8_t symTab[1 << kMaxTableLog];
   uint8_t weights[kMaxSymbols];        // huffman weights
+  uint32_t rankCount[16], rankStart[16];  // huf_build: symbols / cells per weight
 };
 
 // read normalized counts (RFC 8878 4.1.1) from a forward bitstream.
@@ -345,8 +347,6 @@ LSZ_COLD inline int fse_decompress_ws(const uint8_t* src, int64_t n, uint8_t* ds
 // Huffman literals
 // ---------------------------------------------------------------------- //
 
-static const int kHufMaxBits = 11;  // zstd huffman log limit
-
 struct HufEntry {
   uint8_t symbol;
   uint8_t nbBits;
@@ -357,9 +357,16 @@ struct HufTable {  // no default initializers: instances live in LDS
   int maxBits;
 };
 
-// build decode table from weights[0..nsym-1] (HUF_readDTableX1 layout)
-LSZ_COLD inline bool huf_build(HufTable& t, const uint8_t* weights, int nsym) {
-  uint32_t rankCount[kHufMaxBits + 2] = {0};
+// build decode table from weights[0..nsym-1] (HUF_readDTableX1 layout).
+// The per-weight counters are indexed by data, so they live in ws (LDS on
+// the device) and not in locals: as locals they went to per-lane scratch
+// memory, a round trip to global memory for every symbol.
+LSZ_COLD inline bool huf_build(HufTable& t, const uint8_t* weights, int nsym,
+                               BuildWs& ws) {
+  static_assert(kHufMaxBits + 2 <= 16, "rank arrays");
+  uint32_t* rankCount = ws.rankCount;
+  uint32_t* rankStart = ws.rankStart;
+  for (int w = 0; w < kHufMaxBits + 2; w++) rankCount[w] = rankStart[w] = 0;
   uint32_t total = 0;
   for (int s = 0; s < nsym; s++) {
     if (weights[s] > kHufMaxBits) return false;
@@ -379,7 +386,6 @@ LSZ_COLD inline bool huf_build(HufTable& t, const uint8_t* weights, int nsym) {
   // table fill: symbols of weight w occupy 2^(w-1) scaled cells; cells
   // are assigned in weight order (low weight = long codes first),
   // symbols of equal weight in symbol order
-  uint32_t rankStart[kHufMaxBits + 2] = {0};
   {
     uint32_t cur = 0;
     for (int w = 1; w <= maxBits; w++) {
@@ -625,7 +631,7 @@ LSZ_HD inline int64_t read_huf_tree(const uint8_t* p, int64_t rem,
     nw = fse_decompress_ws(p + 1, hb, ws.weights, 255, ws);
     if (nw < 0) return -1;
   }
-  return huf_build(t, ws.weights, nw) ? used : -1;
+  return huf_build(t, ws.weights, nw, ws) ? used : -1;
 }
 
 struct HufStream {
@@ -669,6 +675,48 @@ LSZ_HD inline int read_seq_count(const uint8_t* p, int64_t rem, int64_t& nSeq) {
   if (rem < 3) return -1;
   nSeq = p[1] + ((int64_t)p[2] << 8) + 0x7F00;
   return 3;
+}
+
+static const int64_t kHufOnlyMax = 1 << 17;  // largest Huffman-only page
+
+struct HufOnly {
+  int nStreams;     // 1 or 4
+  int sizeFormat;   // literals header form (10-, 14- or 18-bit sizes)
+  int64_t rs;       // regenerated bytes, equals the page's uncompressed size
+  int64_t payload;  // src[payload .. payload + cs): tree description, streams
+  int64_t cs;
+};
+
+// Is src[0..n) a Huffman-only page of `rs` bytes? That is one frame without
+// a dictionary id, holding one last compressed block whose literals have
+// their own tree and regenerate all `rs` bytes in 1 or 4 streams, followed
+// by a sequence count of zero and nothing else. Answered from the header
+// bytes; builds no table. Such a page needs no FSE sequence decode, no
+// match copy and no window: csrc/cpp/huf_par.h decodes it.
+LSZ_HD inline bool huf_only_frame(const uint8_t* src, int64_t n, int64_t rs,
+                                  HufOnly& out) {
+  if (n < 5 || rs <= 0 || rs > kHufOnlyMax) return false;
+  bool skippable, checksum;
+  int64_t ip = parse_frame_header(src, n, 0, skippable, checksum);
+  if (ip < 0 || skippable || (src[4] & 3) != 0) return false;
+  BlockHdr b;
+  if (!parse_block_header(src + ip, n - ip, b)) return false;
+  if (!b.last || b.type != kBlockCompressed) return false;
+  ip += 3;
+  if (ip + b.size + (checksum ? 4 : 0) != n) return false;  // one frame only
+  LitHdr h;
+  if (!parse_literals_header(src + ip, b.size, h)) return false;
+  if (h.type != kLitCompressed || h.rs != rs) return false;
+  int64_t nSeq;
+  int64_t lit = h.hdr + h.cs;
+  int used = read_seq_count(src + ip + lit, b.size - lit, nSeq);
+  if (used < 0 || nSeq != 0 || lit + used != b.size) return false;
+  out.nStreams = h.nStreams;
+  out.sizeFormat = h.sizeFormat;
+  out.rs = rs;
+  out.payload = ip + h.hdr;
+  out.cs = h.cs;
+  return true;
 }
 
 enum { kSeqLL = 0, kSeqOF = 1, kSeqML = 2 };  // table kinds

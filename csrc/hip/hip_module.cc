@@ -683,10 +683,60 @@ static torch::Tensor zstd_decompress_into(torch::Tensor src, torch::Tensor jobs,
   return status;
 }
 
+// the host-filled byte ranges [a, b) of a unit's values buffer, host to
+// device on the current stream, in one GIL-free call: a unit whose pages
+// decompress on the GPU leaves two such ranges per file, and as python
+// slice copies they held the interpreter lock for 0.7 ms per unit
+// (profiles/r03_gpu_huf.md). Tensor copies, so that the pinned buffer's
+// allocator learns of the stream that still reads it.
+static void copy_ranges_h2d(torch::Tensor host, torch::Tensor dev,
+                            torch::Tensor ranges) {
+  CHECK_GPU(dev);
+  TORCH_CHECK(!host.is_cuda() && host.dim() == 1 && dev.dim() == 1 &&
+                  host.scalar_type() == dev.scalar_type() &&
+                  host.numel() == dev.numel(),
+              "copy_ranges_h2d: two 1-d buffers of one size and type");
+  TORCH_CHECK(!ranges.is_cuda() && ranges.scalar_type() == torch::kInt64 &&
+                  ranges.dim() == 2 && ranges.size(1) == 2 &&
+                  ranges.is_contiguous(),
+              "copy_ranges_h2d: ranges is a host int64 [m][2]");
+  const int64_t* r = ranges.data_ptr<int64_t>();
+  const int64_t m = ranges.size(0), n = host.numel();
+  for (int64_t i = 0; i < m; i++)
+    TORCH_CHECK(0 <= r[2 * i] && r[2 * i] <= r[2 * i + 1] && r[2 * i + 1] <= n,
+                "copy_ranges_h2d: range outside the buffer");
+  py::gil_scoped_release rel;
+  for (int64_t i = 0; i < m; i++) {
+    int64_t a = r[2 * i], len = r[2 * i + 1] - a;
+    if (len > 0) dev.narrow(0, a, len).copy_(host.narrow(0, a, len), true);
+  }
+}
+
+// GPU decode of Huffman-only zstd pages (zstd_huf.hip): a workgroup per
+// Huffman stream, straight into dst; no scratch. status[i] != 0: page i is
+// not a valid Huffman-only page (part of its own range may be written).
+static torch::Tensor zstd_huf_decompress_into(torch::Tensor src,
+                                              torch::Tensor jobs,
+                                              torch::Tensor dst) {
+  CHECK_GPU(src);
+  CHECK_GPU(jobs);
+  CHECK_GPU(dst);
+  TORCH_CHECK(jobs.dim() == 2 && jobs.size(1) == 4 && jobs.is_contiguous(),
+              "jobs must be a contiguous [m][4] table");
+  int64_t njobs = jobs.size(0);
+  auto status = torch::empty({njobs}, src.options().dtype(torch::kInt32));
+  launch_zstd_huf_decompress(src.data_ptr<uint8_t>(), jobs.data_ptr<int64_t>(),
+                             njobs, dst.data_ptr<uint8_t>(),
+                             status.data_ptr<int32_t>(), cur_stream());
+  return status;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ann_scores", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, false); });
   m.def("ann_scores_t", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, true); });
   m.def("zstd_decompress_into", &zstd_decompress_into);
+  m.def("zstd_huf_decompress_into", &zstd_huf_decompress_into);
+  m.def("copy_ranges_h2d", &copy_ranges_h2d);
   m.def("str_chunk_keys", [](torch::Tensor offsets, torch::Tensor bytes,
                              int64_t chunk) {
     CHECK_GPU(offsets);

@@ -110,7 +110,7 @@ void launch_byte_stream_split(const uint8_t* payload, int64_t vals_len,
                               const int64_t* pages, int64_t npages, T* out,
                               int64_t dense_n, hipStream_t s);
 
-// snappy.hip, zstd.hip
+// snappy.hip, zstd.hip, zstd_huf.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,
                               hipStream_t s);
@@ -118,5 +118,11 @@ void launch_zstd_decompress(const uint8_t* src, const int64_t* jobs,
                             int64_t njobs, uint8_t* dst, uint8_t* scratch,
                             int64_t nblocks, int32_t* status, hipStream_t s);
 int64_t lsz_gpu_litbuf_bytes();
+// Huffman-only zstd pages (lszstd::huf_only_frame); any other page gets
+// status 1 (a page whose streams are not all valid may be partly written,
+// inside its own output range)
+void launch_zstd_huf_decompress(const uint8_t* src, const int64_t* jobs,
+                                int64_t njobs, uint8_t* dst, int32_t* status,
+                                hipStream_t s);
 
 }  // namespace lakesoul

@@ -89,13 +89,21 @@ _GPU_ZSTD = _GPU_ZSTD_FRAC > 0.0
 # 1.4x-7x the host route); no scan-level A/B has been measured.
 _GPU_DELTA = _os.environ.get("LAKESOUL_GPU_DELTA", "1") != "0"
 
+# Huffman-only zstd pages (one compressed block, Huffman literals, no
+# sequences: float columns, wide-range integers) decode on the GPU, 256
+# lanes per Huffman stream (csrc/hip/zstd_huf.hip), and leave the host pool;
+# the unit's other pages follow LAKESOUL_GPU_ZSTD* as before.
+# LAKESOUL_GPU_HUF=0 sends them back to where they went without it.
+# Measured: profiles/r03_gpu_huf.md.
+_GPU_HUF = _os.environ.get("LAKESOUL_GPU_HUF", "1") != "0"
+
 
 def fetch_raw(files: List[str], names: List[str]) -> dict:
     """Host phase of a unit read (releases the GIL in C++) — safe to run
     on a prefetch thread while the GPU processes the previous unit."""
     with timing.phase("host_fetch"):
         raw = cpp().read_unit_raw(files, names, 0, True, True, _GPU_ZSTD,
-                                  _GPU_ZSTD_FRAC, _GPU_DELTA)
+                                  _GPU_ZSTD_FRAC, _GPU_DELTA, _GPU_HUF)
     if timing.ENABLED:
         timing._acc["fetch.stage1"] += raw["t_stage1_us"] / 1e6
         timing._acc["fetch.s1_open"] += raw["t_open_us"] / 1e6
@@ -119,7 +127,7 @@ class UnitTransfer:
         # data — ship only the host-filled gaps (for all-zstd units the
         # H2D volume drops to the compressed bytes)
         jobs_host = []
-        for k in ("snappy_jobs", "zstd_jobs"):
+        for k in ("snappy_jobs", "zstd_jobs", "huf_jobs"):
             t = raw.get(k)
             if t is not None and t.numel():
                 jobs_host.append(t.view(-1, 4))
@@ -135,9 +143,9 @@ class UnitTransfer:
             gap_ends = np.concatenate((dst, [nvals]))
             keep = gap_ends > gap_starts
             self.vals = torch.empty(nvals, dtype=torch.uint8, device=device)
-            hv = raw["values"]
-            for a, b in zip(gap_starts[keep], gap_ends[keep]):
-                self.vals[a:b].copy_(hv[a:b], non_blocking=True)
+            gaps = np.stack((gap_starts[keep], gap_ends[keep]), axis=1)
+            hip().copy_ranges_h2d(raw["values"], self.vals,
+                                  torch.from_numpy(gaps.astype(np.int64)))
         else:
             self.vals = raw["values"].to(device, non_blocking=True)
         self.validity = (
@@ -165,6 +173,19 @@ class UnitTransfer:
             if raw.get("zstd_jobs") is not None and raw["zstd_jobs"].numel()
             else None
         )
+        self.huf_jobs = (
+            raw["huf_jobs"].view(-1, 4).to(device, non_blocking=True)
+            if raw.get("huf_jobs") is not None and raw["huf_jobs"].numel()
+            else None
+        )
+
+
+def _check_huf_status(status) -> None:
+    """Raise if the Huffman kernel refused a page. Called once the unit's
+    decode has synchronized anyway: no host sync of its own per unit."""
+    if status is not None and bool((status != 0).any()):
+        raise RuntimeError(
+            f"GPU zstd Huffman decode failed: status={int((status != 0).sum())} pages")
 
 
 def _wrap_column(f, entry) -> Column:
@@ -227,6 +248,11 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
         status = hip().zstd_decompress_into(transfer.comp, transfer.zstd_jobs, vals)
         if bool((status != 0).any()):
             raise RuntimeError(f"GPU zstd decompression failed: status={int((status != 0).sum())} pages")
+    huf_status = None
+    if transfer.huf_jobs is not None:
+        # Huffman-only zstd pages: a workgroup per page, straight into the
+        # values buffer; the status is read after the unit's decode
+        huf_status = hip().zstd_huf_decompress_into(transfer.comp, transfer.huf_jobs, vals)
 
     fields = [scan._field_for(n) for n in names]
     has_list = any(f.dtype.startswith("list<") for f in fields)
@@ -266,6 +292,7 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
             pk_es = 8 if scan.schema.field(scan.pk[0]).dtype == "int64" else 4
             outs = hip().scan_unit_uselast(*unit_bufs, pk_ci, pk_es,
                                            transfer.enc)
+        _check_huf_status(huf_status)
         merged = {f.name: _wrap_column(f, outs[ci])
                   for ci, f in enumerate(fields)}
         return scan._to_eval_batch(merged, unit, len(merged[names[0]]), device)
@@ -275,6 +302,7 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
     present: List[set] = []
     with timing.phase("gpu_decode", sync_gpu=True):
         outs = hip().decode_unit(*unit_bufs, transfer.enc)
+        _check_huf_status(huf_status)
         for fi, nrows in enumerate(raw["file_rows"]):
             cols: Dict[str, Column] = {}
             pres = set()
