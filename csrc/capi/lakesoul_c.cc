@@ -890,6 +890,7 @@ extern "C" LakesoulCWriter* lakesoul_c_writer_create_from_config(
   w->path = path;
   std::string codec = c->get("compression", "zstd");
   if (codec == "none" || codec == "uncompressed") w->codec = CODEC_UNCOMPRESSED;
+  else if (codec == "lz4_raw" || codec == "lz4") w->codec = CODEC_LZ4_RAW;
   std::string lvl = c->get("compression_level");
   if (!lvl.empty()) w->level = std::stoi(lvl);
   std::string rg = c->get("max_row_group_size");
@@ -901,6 +902,7 @@ extern "C" int lakesoul_c_writer_set_compression(LakesoulCWriter* w, const char*
   std::string c = codec;
   if (c == "zstd") w->codec = CODEC_ZSTD;
   else if (c == "none" || c == "uncompressed") w->codec = CODEC_UNCOMPRESSED;
+  else if (c == "lz4_raw" || c == "lz4") w->codec = CODEC_LZ4_RAW;
   else {
     g_err = "unsupported codec " + c;
     return -1;

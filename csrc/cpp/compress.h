@@ -1,7 +1,8 @@
 // Compression codecs: zstd via libzstd.so.1 (prototypes declared here —
-// the image has the runtime lib but no dev header), snappy decode
-// implemented from the format spec (the reference's default codec is
-// zstd(1), writer/mod.rs:224-245; snappy read support is for foreign files).
+// the image has the runtime lib but no dev header), snappy decode and the
+// LZ4 block codec implemented from the format specs (the reference's
+// default codec is zstd(1), writer/mod.rs:224-245; snappy read support is
+// for foreign files; LZ4_RAW is read and written, lz4_dec.h).
 #pragma once
 
 #include <cstddef>
@@ -10,6 +11,8 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "lz4_dec.h"
 
 extern "C" {
 size_t ZSTD_compress(void* dst, size_t dstCapacity, const void* src,
@@ -95,6 +98,25 @@ inline void snappy_decompress_into(uint8_t* dst, size_t dst_n,
   if (d != dend) throw std::runtime_error("snappy: short output");
 }
 
+// -- LZ4 blocks (lz4_dec.h): codec 7 is one raw block per page, codec 5 the
+// deprecated Hadoop framing around such blocks. The level is ignored.
+
+inline std::vector<uint8_t> lz4_compress(const uint8_t* src, size_t n) {
+  return lslz4::lz4_block_encode(src, n);
+}
+
+inline void lz4_decompress_into(uint8_t* dst, size_t dst_n, const uint8_t* src,
+                                size_t src_n) {
+  if (!lslz4::lz4_block_decode(dst, (int64_t)dst_n, src, (int64_t)src_n))
+    throw std::runtime_error("lz4 decompress failed");
+}
+
+inline void lz4_hadoop_decompress_into(uint8_t* dst, size_t dst_n,
+                                       const uint8_t* src, size_t src_n) {
+  if (!lslz4::lz4_hadoop_decode(dst, (int64_t)dst_n, src, (int64_t)src_n))
+    throw std::runtime_error("lz4 (hadoop) decompress failed");
+}
+
 inline void decompress_into(int codec, uint8_t* dst, size_t dst_n,
                             const uint8_t* src, size_t src_n) {
   switch (codec) {
@@ -105,8 +127,14 @@ inline void decompress_into(int codec, uint8_t* dst, size_t dst_n,
     case 1:  // SNAPPY
       snappy_decompress_into(dst, dst_n, src, src_n);
       return;
+    case 5:  // LZ4 (Hadoop framing, or a raw block from old writers)
+      lz4_hadoop_decompress_into(dst, dst_n, src, src_n);
+      return;
     case 6:  // ZSTD
       zstd_decompress_into(dst, dst_n, src, src_n);
+      return;
+    case 7:  // LZ4_RAW
+      lz4_decompress_into(dst, dst_n, src, src_n);
       return;
     default:
       throw std::runtime_error("unsupported parquet codec " + std::to_string(codec));

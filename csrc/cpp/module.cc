@@ -588,14 +588,14 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
                                  const std::vector<std::string>& names,
                                  int64_t nthreads, bool pin, bool gpu_snappy,
                                  bool gpu_zstd, double gpu_zstd_frac,
-                                 bool gpu_delta, bool gpu_huf) {
+                                 bool gpu_delta, bool gpu_huf, bool gpu_lz4) {
   (void)nthreads;
   std::unique_ptr<UnitStage> st;
   auto t0 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
     st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac,
-                          gpu_delta, gpu_huf);
+                          gpu_delta, gpu_huf, gpu_lz4);
   }
   auto t1 = std::chrono::steady_clock::now();
   UnitStage& ud = *st;
@@ -629,6 +629,9 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   torch::Tensor hjobs = torch::empty({(int64_t)ud.huf_jobs.size()}, torch::kInt64);
   if (!ud.huf_jobs.empty())
     std::memcpy(hjobs.data_ptr(), ud.huf_jobs.data(), ud.huf_jobs.size() * 8);
+  torch::Tensor ljobs = torch::empty({(int64_t)ud.lz4_jobs.size()}, torch::kInt64);
+  if (!ud.lz4_jobs.empty())
+    std::memcpy(ljobs.data_ptr(), ud.lz4_jobs.data(), ud.lz4_jobs.size() * 8);
   auto t2 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
@@ -657,6 +660,7 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   d["snappy_jobs"] = sjobs;
   d["zstd_jobs"] = zjobs;
   d["huf_jobs"] = hjobs;
+  d["lz4_jobs"] = ljobs;
   py::list frows;
   for (auto r : ud.file_rows) frows.append(r);
   d["file_rows"] = frows;
@@ -893,7 +897,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nthreads") = 0, py::arg("pin") = true,
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
         py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false,
-        py::arg("gpu_huf") = false);
+        py::arg("gpu_huf") = false, py::arg("gpu_lz4") = false);
   // the one descriptor column python looks at (fast-path eligibility)
   m.attr("UD_PRESENT") = (int)UD_PRESENT;
   // where a column's regions lie, and its GPU-decoded value encoding
@@ -935,6 +939,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                out.data(), cap, ctx.get());
     if (n < 0) throw std::runtime_error("lszstd decode failed");
     return py::bytes((const char*)out.data(), (size_t)n);
+  });
+  // the LZ4 block codec (lz4_dec.h): decoder hooks return None for a block
+  // they refuse
+  m.def("lz4_block_decode_ref", [](py::bytes src, int64_t n) -> py::object {
+    std::string b = src;
+    if (n < 0) throw std::runtime_error("lz4_block_decode_ref: n < 0");
+    std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)n ? (size_t)n : 1]);
+    if (!lslz4::lz4_block_decode(out.get(), n, (const uint8_t*)b.data(),
+                                 (int64_t)b.size()))
+      return py::none();
+    return py::bytes((const char*)out.get(), (size_t)n);
+  });
+  m.def("lz4_hadoop_decode_ref", [](py::bytes src, int64_t n) -> py::object {
+    std::string b = src;
+    if (n < 0) throw std::runtime_error("lz4_hadoop_decode_ref: n < 0");
+    std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)n ? (size_t)n : 1]);
+    if (!lslz4::lz4_hadoop_decode(out.get(), n, (const uint8_t*)b.data(),
+                                  (int64_t)b.size()))
+      return py::none();
+    return py::bytes((const char*)out.get(), (size_t)n);
+  });
+  m.def("lz4_compress_ref", [](py::bytes src) {
+    std::string b = src;
+    auto out = lz4_compress((const uint8_t*)b.data(), b.size());
+    return py::bytes((const char*)out.data(), out.size());
   });
   m.def("zstd_frame_census", [](py::bytes bytes) {
     // what format features the frames in `bytes` use: walks them with the

@@ -380,8 +380,12 @@ class ParquetWriter {
           compressed = zstd_compress(payload.data(), payload.size(), level_);
           body = compressed.data();
           body_n = compressed.size();
+        } else if (codec_ == CODEC_LZ4_RAW) {
+          compressed = lz4_compress(payload.data(), payload.size());
+          body = compressed.data();
+          body_n = compressed.size();
         } else if (codec_ != CODEC_UNCOMPRESSED) {
-          throw std::runtime_error("writer supports zstd/uncompressed only");
+          throw std::runtime_error("writer supports zstd/lz4_raw/uncompressed only");
         }
 
         // ---- page header + emit ----
@@ -501,8 +505,12 @@ class ParquetWriter {
       compressed = zstd_compress(payload.data(), payload.size(), level_);
       body = compressed.data();
       body_n = compressed.size();
+    } else if (codec_ == CODEC_LZ4_RAW) {
+      compressed = lz4_compress(payload.data(), payload.size());
+      body = compressed.data();
+      body_n = compressed.size();
     } else if (codec_ != CODEC_UNCOMPRESSED) {
-      throw std::runtime_error("writer supports zstd/uncompressed only");
+      throw std::runtime_error("writer supports zstd/lz4_raw/uncompressed only");
     }
 
     ColumnMeta cm;
@@ -759,6 +767,9 @@ class ParquetFile {
     // gpu_compressed chunk (lszstd::huf_only_frame), by file offset like
     // defer_pages: the GPU decodes them (csrc/hip/zstd_huf.hip)
     std::vector<DeferPage> huf_pages;
+    // gpu_lz4 mode: the LZ4_RAW pages of a host_deferred chunk, by file
+    // offset: the GPU decodes them (csrc/hip/lz4.hip)
+    std::vector<DeferPage> lz4_pages;
     // LIST columns: rows -> element ranges (+1 sentinel) and per-row
     // validity; values/validity above then describe the ELEMENTS
     bool is_list = false;
@@ -820,24 +831,31 @@ class ParquetFile {
   // gpu_huf (with defer_host or gpu_zstd): decided per page. A zstd page
   // that could be deferred and is Huffman-only goes to huf_pages; the
   // chunk's other pages follow the other flags as without it.
+  // gpu_lz4: LZ4_RAW pages under the snappy route's conditions go to
+  // lz4_pages by file offset (csrc/hip/lz4.hip decodes them); the chunk is
+  // host_deferred with no payload, so its descriptor is cached.
   ChunkData read_chunk(size_t rg, size_t col, bool gpu_snappy = false,
                        bool defer_host = false, bool gpu_zstd = false,
-                       bool gpu_delta = false, bool gpu_huf = false) const {
+                       bool gpu_delta = false, bool gpu_huf = false,
+                       bool gpu_lz4 = false) const {
     gpu_huf = gpu_huf && (defer_host || gpu_zstd);
     // descriptor cache: lakehouse files are immutable, and deferred /
     // gpu-staged chunks are pure page descriptors (no payload) — cache
     // them so repeated scans skip the per-page thrift header walk
     // (reference analog: the global metadata cache, session.rs:86-105)
-    uint64_t ckey = ((uint64_t)rg << 24) | ((uint64_t)col << 4) |
+    // (five flag bits below the column index)
+    uint64_t ckey = ((uint64_t)rg << 25) | ((uint64_t)col << 5) |
                     (defer_host ? 1u : 0u) | (gpu_snappy ? 2u : 0u) |
-                    (gpu_zstd ? 4u : 0u) | (gpu_huf ? 8u : 0u);
-    if (defer_host || gpu_snappy || gpu_zstd) {
+                    (gpu_zstd ? 4u : 0u) | (gpu_huf ? 8u : 0u) |
+                    (gpu_lz4 ? 16u : 0u);
+    if (defer_host || gpu_snappy || gpu_zstd || gpu_lz4) {
       std::lock_guard<std::mutex> lk(chunk_mu_);
       auto it = chunk_meta_cache_.find(ckey);
       if (it != chunk_meta_cache_.end()) return *it->second;
     }
     ChunkData out_cached = read_chunk_impl(rg, col, gpu_snappy, defer_host,
-                                           gpu_zstd, gpu_delta, gpu_huf);
+                                           gpu_zstd, gpu_delta, gpu_huf,
+                                           gpu_lz4);
     if ((out_cached.host_deferred || out_cached.gpu_compressed) &&
         out_cached.values.empty() && out_cached.validity.empty() &&
         out_cached.dict.empty() && out_cached.comp.empty()) {
@@ -852,7 +870,8 @@ class ParquetFile {
                             bool defer_host = false,
                             bool gpu_zstd = false,
                             bool gpu_delta = false,
-                            bool gpu_huf = false) const {
+                            bool gpu_huf = false,
+                            bool gpu_lz4 = false) const {
     const RowGroup& g = meta_.row_groups.at(rg);
     const ColumnMeta& cm = g.columns.at(col);
     const ColumnDesc& cd = cols_.at(col);
@@ -938,6 +957,26 @@ class ParquetFile {
         values_seen += ph.num_values;
         continue;
       }
+      if (gpu_lz4 && cm.codec == CODEC_LZ4_RAW && ph.type == PAGE_DATA &&
+          ph.encoding == ENC_PLAIN && !cd.nullable &&
+          cd.physical != PT_BOOLEAN && cd.physical != PT_BYTE_ARRAY &&
+          cd.physical != PT_FLBA && cd.physical != PT_INT96 && !cd.is_list &&
+          out.dict.empty() && out.values.empty()) {
+        // by file offset, like huf_pages: no body is copied here. A later
+        // page of the chunk that does not qualify trips the host_deferred
+        // check below and the chunk is redone on the host.
+        out.host_deferred = true;
+        DeferPage dp;
+        dp.file_off = (int64_t)(body - map_);
+        dp.comp_len = ph.compressed_size;
+        dp.out_off = out.values_len;
+        dp.out_len = ph.uncompressed_size;
+        dp.codec = cm.codec;
+        out.lz4_pages.push_back(dp);
+        out.values_len += ph.uncompressed_size;
+        values_seen += ph.num_values;
+        continue;
+      }
       if (((gpu_snappy && cm.codec == CODEC_SNAPPY) ||
            (gpu_zstd && cm.codec == CODEC_ZSTD &&
             ph.uncompressed_size <= (512 << 10))) &&
@@ -959,7 +998,8 @@ class ParquetFile {
         continue;
       }
       if (defer_host &&
-          (cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED) &&
+          (cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED ||
+           cm.codec == CODEC_LZ4_RAW) &&
           ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN && !cd.nullable &&
           cd.physical != PT_BOOLEAN && cd.physical != PT_BYTE_ARRAY &&
           cd.physical != PT_FLBA && cd.physical != PT_INT96 && !cd.is_list &&
@@ -979,7 +1019,8 @@ class ParquetFile {
         continue;
       }
       if (out.host_deferred &&
-          !((cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED) &&
+          !((cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED ||
+             cm.codec == CODEC_LZ4_RAW) &&
             ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN)) {
         return read_chunk_impl(rg, col, false, false);  // mixed: redo staged
       }

@@ -161,6 +161,10 @@ struct UnitStage {
   // dst_off = its place in comp)
   std::vector<int64_t> huf_jobs;
   std::vector<HostJob> huf_src;
+  // LZ4_RAW pages, decoded by lz4.hip: jobs as snappy_jobs; lz4_src as
+  // huf_src (the two share the tail of comp)
+  std::vector<int64_t> lz4_jobs;
+  std::vector<HostJob> lz4_src;
   std::vector<std::unique_ptr<StrDecoded>> str_cols;
   int64_t values_size = 0, validity_size = 0, dicts_size = 0, soffs_size = 0,
           comp_size = 0;
@@ -169,7 +173,8 @@ struct UnitStage {
 inline std::unique_ptr<UnitStage> read_unit_stage1(
     const std::vector<std::string>& paths, const std::vector<std::string>& names,
     bool gpu_snappy = false, bool gpu_zstd = false,
-    double gpu_zstd_frac = 1.0, bool gpu_delta = false, bool gpu_huf = false) {
+    double gpu_zstd_frac = 1.0, bool gpu_delta = false, bool gpu_huf = false,
+    bool gpu_lz4 = false) {
   auto st = std::make_unique<UnitStage>();
   UnitStage& S = *st;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -219,7 +224,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
             gpu_zstd && ((double)((i * 2654435761u) % 1000) < gpu_zstd_frac * 1000.0);
         fd.chunks[t.c][t.rg] =
             fd.f->read_chunk(t.rg, fd.col_idx[t.c], gpu_snappy, true, this_gpu_zstd,
-                             gpu_delta, gpu_huf);
+                             gpu_delta, gpu_huf, gpu_lz4);
       } catch (std::exception& e) {
         std::lock_guard<std::mutex> lk(err_mu);
         err = e.what();
@@ -269,7 +274,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
 
   // layout
   int64_t vpos = 0, vapos = 0, dpos = 0, spos = 0;
-  int64_t huf_comp = 0;  // bytes of Huffman-only frames so far
+  int64_t huf_comp = 0;  // bytes of Huffman-only frames and LZ4 blocks so far
   for (size_t fi = 0; fi < nfiles; fi++) {
     auto& fd = S.files[fi];
     for (size_t c = 0; c < names.size(); c++) {
@@ -436,6 +441,14 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
                 {(int)fi, hp.file_off, hp.comp_len, huf_comp, hp.out_len, hp.codec});
             huf_comp += hp.comp_len;
           }
+          for (auto& lp : ch.lz4_pages) {
+            S.lz4_jobs.insert(S.lz4_jobs.end(),
+                              {huf_comp, lp.comp_len, vpos + plen + lp.out_off,
+                               lp.out_len});
+            S.lz4_src.push_back(
+                {(int)fi, lp.file_off, lp.comp_len, huf_comp, lp.out_len, lp.codec});
+            huf_comp += lp.comp_len;
+          }
           if (ch.gpu_compressed) {
             for (auto& cp : ch.comp_pages) {
               auto& jobs = (cp.codec == CODEC_ZSTD) ? S.zstd_jobs : S.snappy_jobs;
@@ -521,10 +534,15 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     }
   }
 
-  // the Huffman-only frames go behind the chunk-owned page bodies in comp
+  // the Huffman-only frames and the LZ4 blocks go behind the chunk-owned
+  // page bodies in comp
   for (size_t i = 0; i < S.huf_src.size(); i++) {
     S.huf_jobs[4 * i] += S.comp_size;
     S.huf_src[i].dst_off += S.comp_size;
+  }
+  for (size_t i = 0; i < S.lz4_src.size(); i++) {
+    S.lz4_jobs[4 * i] += S.comp_size;
+    S.lz4_src[i].dst_off += S.comp_size;
   }
   S.comp_size += huf_comp;
 
@@ -612,13 +630,16 @@ inline void read_unit_fill(UnitStage& S, uint8_t* values, uint8_t* validity,
   // deferred pages: decompress straight from the file mmap into the
   // destination buffer (one pass, zero staging)
   // and, in the same sweep of the pool, the frames of the Huffman-only
-  // pages from the mmap into comp for the GPU (tens of MB per unit: not
-  // for the serial copy above)
+  // pages and the LZ4 blocks from the mmap into comp for the GPU (tens of
+  // MB per unit: not for the serial copy above)
   const int64_t nhost = (int64_t)S.host_jobs.size();
   const int64_t nhuf = comp ? (int64_t)S.huf_src.size() : 0;
-  ThreadPool::instance().parallel_for(nhost + nhuf, [&](int64_t i) {
+  const int64_t nlz4 = comp ? (int64_t)S.lz4_src.size() : 0;
+  ThreadPool::instance().parallel_for(nhost + nhuf + nlz4, [&](int64_t i) {
     if (i >= nhost) {
-      const UnitStage::HostJob& hs = S.huf_src[i - nhost];
+      const UnitStage::HostJob& hs = i - nhost < nhuf
+                                         ? S.huf_src[i - nhost]
+                                         : S.lz4_src[i - nhost - nhuf];
       std::memcpy(comp + hs.dst_off,
                   S.files[hs.file_idx].f->data_at(hs.file_off),
                   (size_t)hs.comp_len);

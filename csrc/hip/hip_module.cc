@@ -731,6 +731,32 @@ static torch::Tensor zstd_huf_decompress_into(torch::Tensor src,
   return status;
 }
 
+// GPU LZ4 (lz4.hip): LZ4_RAW page blocks, one wave per page, no scratch.
+// jobs as for snappy. lz4_decompress_into writes into an existing device
+// buffer; lz4_decompress allocates total_dst bytes and returns
+// (dst, status) for direct tests. status[i] != 0: page i is not a valid
+// block (part of its own output range may be written).
+static torch::Tensor lz4_decompress_into(torch::Tensor src, torch::Tensor jobs,
+                                         torch::Tensor dst) {
+  CHECK_GPU(src);
+  CHECK_GPU(jobs);
+  CHECK_GPU(dst);
+  TORCH_CHECK(jobs.dim() == 2 && jobs.size(1) == 4 && jobs.is_contiguous(),
+              "jobs must be a contiguous [m][4] table");
+  auto status = torch::empty({jobs.size(0)}, src.options().dtype(torch::kInt32));
+  launch_lz4_decompress(src.data_ptr<uint8_t>(), jobs.data_ptr<int64_t>(),
+                        jobs.size(0), dst.data_ptr<uint8_t>(),
+                        status.data_ptr<int32_t>(), cur_stream());
+  return status;
+}
+
+static std::vector<torch::Tensor> lz4_decompress(torch::Tensor src,
+                                                 torch::Tensor jobs,
+                                                 int64_t total_dst) {
+  auto dst = torch::empty({total_dst}, src.options());
+  return {dst, lz4_decompress_into(src, jobs, dst)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ann_scores", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, false); });
   m.def("ann_scores_t", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, true); });
@@ -836,6 +862,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("snappy_decompress", &snappy_decompress);
   m.def("snappy_decompress_into", &snappy_decompress_into);
+  m.def("lz4_decompress", &lz4_decompress);
+  m.def("lz4_decompress_into", &lz4_decompress_into);
   m.def("scan_unit_uselast", &scan_unit_uselast, py::arg("vals"),
         py::arg("validity"), py::arg("dicts"), py::arg("runs"), py::arg("soffs"),
         py::arg("desc"), py::arg("nfiles"), py::arg("ncols"), py::arg("pk_ci"),

@@ -110,10 +110,16 @@ void launch_byte_stream_split(const uint8_t* payload, int64_t vals_len,
                               const int64_t* pages, int64_t npages, T* out,
                               int64_t dense_n, hipStream_t s);
 
-// snappy.hip, zstd.hip, zstd_huf.hip
+// snappy.hip, lz4.hip, zstd.hip, zstd_huf.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,
                               hipStream_t s);
+// LZ4_RAW page blocks; jobs as for snappy. A page that is not a valid
+// block gets a non-zero status (it may be partly written, inside its own
+// output range)
+void launch_lz4_decompress(const uint8_t* src, const int64_t* jobs,
+                           int64_t njobs, uint8_t* dst, int32_t* status,
+                           hipStream_t s);
 void launch_zstd_decompress(const uint8_t* src, const int64_t* jobs,
                             int64_t njobs, uint8_t* dst, uint8_t* scratch,
                             int64_t nblocks, int32_t* status, hipStream_t s);

@@ -29,15 +29,15 @@
 
 #include "../cpp/zstd_dec.h"
 #include "kernels.h"
+#include "wave_copy.h"
 
 namespace lsz_gpu {
 
 using namespace lszstd;
+using namespace lswave;  // waitcnt0, wcopy_wide, wcopy_src
 
 #define LANES 64
 static const int kLitBufCap = 1 << 17;  // 128 KB literals per block
-
-__device__ inline void waitcnt0() { __builtin_amdgcn_s_waitcnt(0); }
 
 // order LDS ops only (lgkmcnt(0); vmcnt=63, expcnt=7 untouched): the
 // window read/write shuffle must not drain in-flight global stores —
@@ -45,46 +45,11 @@ __device__ inline void waitcnt0() { __builtin_amdgcn_s_waitcnt(0); }
 // profiles/r01_gpu_zstd.md)
 __device__ inline void lds_sync() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
-// unaligned-capable wide element copy: 8 bytes per lane per iteration
-// (gfx950 flat loads support byte-aligned addresses), byte tail
-template <bool VOL>
-__device__ inline void wcopy_wide(uint8_t* dst, const uint8_t* src,
-                                  int64_t len, int lane) {
-  int64_t n8 = len >> 3;
-  for (int64_t j = lane; j < n8; j += LANES) {
-    uint64_t w;
-    if (VOL)
-      w = *(const volatile uint64_t*)(src + 8 * j);
-    else
-      __builtin_memcpy(&w, src + 8 * j, 8);
-    *(uint64_t*)(dst + 8 * j) = w;
-  }
-  for (int64_t j = (n8 << 3) + lane; j < len; j += LANES)
-    dst[j] = VOL ? ((volatile const uint8_t*)src)[j] : src[j];
-}
-
 // cooperative copy from the literals scratch (written by this wave
 // earlier — volatile read to bypass stale L1)
 __device__ inline void wcopy_from_lit(uint8_t* dst, const uint8_t* lit,
                                       uint32_t len, int lane) {
   wcopy_wide<true>(dst, lit, len, lane);
-  waitcnt0();
-}
-
-// cooperative (possibly overlapping) match copy inside dst
-__device__ inline void wcopy_match(uint8_t* base, int64_t out, uint32_t offset,
-                                   uint32_t len, int lane) {
-  for (uint32_t j = lane; j < len; j += LANES) {
-    uint32_t sj = (offset >= len) ? j : (j % offset);
-    base[out + j] = ((volatile const uint8_t*)base)[out - offset + sj];
-  }
-  waitcnt0();
-}
-
-// cooperative copy from the (read-only) compressed input
-__device__ inline void wcopy_src(uint8_t* dst, const uint8_t* src,
-                                 int64_t len, int lane) {
-  wcopy_wide<false>(dst, src, len, lane);
   waitcnt0();
 }
 

@@ -23,7 +23,8 @@ from ..ops import cpp
 from .batch import Batch
 from .fs import default_fs
 
-_CODEC_ID = {"zstd": 6, "none": 0, "uncompressed": 0}
+_CODEC_ID = {"zstd": 6, "none": 0, "uncompressed": 0,
+             "lz4_raw": 7, "lz4": 7}  # pyarrow's names for LZ4_RAW
 
 
 class StreamingParquetUpload:

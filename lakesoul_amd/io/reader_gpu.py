@@ -97,13 +97,24 @@ _GPU_DELTA = _os.environ.get("LAKESOUL_GPU_DELTA", "1") != "0"
 # Measured: profiles/r03_gpu_huf.md.
 _GPU_HUF = _os.environ.get("LAKESOUL_GPU_HUF", "1") != "0"
 
+# LZ4_RAW pages of REQUIRED fixed-width PLAIN columns: the host pool decodes
+# them straight into the values buffer, as it does zstd pages.
+# LAKESOUL_GPU_LZ4=1 sends them to the GPU instead, one wave per page
+# (csrc/hip/lz4.hip): their compressed bytes cross the bus and the host
+# never touches them. Off by default: on the headline table the GPU route
+# scans in 252 ms against 28 ms (the kernel walks a page's sequences
+# serially, about 1 us each, and a scan unit holds only a few hundred
+# pages). Measured: profiles/r04_gpu_lz4.md.
+_GPU_LZ4 = _os.environ.get("LAKESOUL_GPU_LZ4", "0") == "1"
+
 
 def fetch_raw(files: List[str], names: List[str]) -> dict:
     """Host phase of a unit read (releases the GIL in C++) — safe to run
     on a prefetch thread while the GPU processes the previous unit."""
     with timing.phase("host_fetch"):
         raw = cpp().read_unit_raw(files, names, 0, True, True, _GPU_ZSTD,
-                                  _GPU_ZSTD_FRAC, _GPU_DELTA, _GPU_HUF)
+                                  _GPU_ZSTD_FRAC, _GPU_DELTA, _GPU_HUF,
+                                  _GPU_LZ4)
     if timing.ENABLED:
         timing._acc["fetch.stage1"] += raw["t_stage1_us"] / 1e6
         timing._acc["fetch.s1_open"] += raw["t_open_us"] / 1e6
@@ -127,7 +138,7 @@ class UnitTransfer:
         # data — ship only the host-filled gaps (for all-zstd units the
         # H2D volume drops to the compressed bytes)
         jobs_host = []
-        for k in ("snappy_jobs", "zstd_jobs", "huf_jobs"):
+        for k in ("snappy_jobs", "zstd_jobs", "huf_jobs", "lz4_jobs"):
             t = raw.get(k)
             if t is not None and t.numel():
                 jobs_host.append(t.view(-1, 4))
@@ -176,6 +187,11 @@ class UnitTransfer:
         self.huf_jobs = (
             raw["huf_jobs"].view(-1, 4).to(device, non_blocking=True)
             if raw.get("huf_jobs") is not None and raw["huf_jobs"].numel()
+            else None
+        )
+        self.lz4_jobs = (
+            raw["lz4_jobs"].view(-1, 4).to(device, non_blocking=True)
+            if raw.get("lz4_jobs") is not None and raw["lz4_jobs"].numel()
             else None
         )
 
@@ -240,6 +256,11 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
         status = hip().snappy_decompress_into(transfer.comp, transfer.snappy_jobs, vals)
         if bool((status != 0).any()):
             raise RuntimeError(f"GPU snappy decompression failed: {status.cpu().tolist()}")
+    if transfer.lz4_jobs is not None:
+        # GPU LZ4: LZ4_RAW page blocks straight into the values buffer
+        status = hip().lz4_decompress_into(transfer.comp, transfer.lz4_jobs, vals)
+        if bool((status != 0).any()):
+            raise RuntimeError(f"GPU lz4 decompression failed: status={int((status != 0).sum())} pages")
     if transfer.zstd_jobs is not None:
         # GPU zstd: the from-scratch RFC 8878 decoder (csrc/hip/zstd.hip)
         # decompresses zstd page frames straight into the values buffer —

@@ -31,7 +31,8 @@ from .batch import Batch, Column
 from .fs import default_fs, is_remote
 from .schema import Schema
 
-_CODEC_ID = {"zstd": 6, "none": 0, "uncompressed": 0}
+_CODEC_ID = {"zstd": 6, "none": 0, "uncompressed": 0,
+             "lz4_raw": 7, "lz4": 7}  # pyarrow's names for LZ4_RAW
 
 
 @dataclass

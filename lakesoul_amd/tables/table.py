@@ -64,6 +64,14 @@ class LakeSoulTable:
             range_partitions=self.range_keys,
             hash_bucket_num=self.hash_bucket_num,
         )
+        # table properties "compression" (zstd, lz4_raw/lz4, none) and
+        # "compression_level" choose the codec of every file the table's
+        # writes, streaming uploads and compactions produce
+        props = self.info.get_properties()
+        if "compression" in props:
+            cfg.compression = str(props["compression"])
+        if "compression_level" in props:
+            cfg.compression_level = int(props["compression_level"])
         for k, v in overrides.items():
             setattr(cfg, k, v)
         return cfg

@@ -45,6 +45,7 @@ if _WITH_HIP:
                 os.path.join("csrc", "hip", "ann.hip"),
                 os.path.join("csrc", "hip", "fastscan.hip"),
                 os.path.join("csrc", "hip", "snappy.hip"),
+                os.path.join("csrc", "hip", "lz4.hip"),
                 os.path.join("csrc", "hip", "zstd.hip"),
                 os.path.join("csrc", "hip", "zstd_huf.hip"),
                 os.path.join("csrc", "hip", "delta.hip"),
