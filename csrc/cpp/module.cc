@@ -14,6 +14,8 @@
 #include "murmur3.h"
 #include "parquet_file.h"
 #include "read_unit.h"
+#include "str_seg.h"
+#include "str_walk.h"
 #include "unit_desc.h"
 #include "huf_par.h"
 #include "zstd_dec.h"
@@ -588,14 +590,15 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
                                  const std::vector<std::string>& names,
                                  int64_t nthreads, bool pin, bool gpu_snappy,
                                  bool gpu_zstd, double gpu_zstd_frac,
-                                 bool gpu_delta, bool gpu_huf, bool gpu_lz4) {
+                                 bool gpu_delta, bool gpu_huf, bool gpu_lz4,
+                                 bool gpu_strings) {
   (void)nthreads;
   std::unique_ptr<UnitStage> st;
   auto t0 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
     st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac,
-                          gpu_delta, gpu_huf, gpu_lz4);
+                          gpu_delta, gpu_huf, gpu_lz4, gpu_strings);
   }
   auto t1 = std::chrono::steady_clock::now();
   UnitStage& ud = *st;
@@ -692,6 +695,7 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
     da[i][UD_ENC_OFF] = c.enc_off;
     da[i][UD_ENC_CNT] = c.enc_cnt;
     da[i][UD_ENC_PAGES] = c.enc_pages;
+    da[i][UD_STR] = c.str_kind;
   }
   d["desc"] = dt;
   // free the staging structures (dozens of MB of chunk vectors) off the
@@ -897,7 +901,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nthreads") = 0, py::arg("pin") = true,
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
         py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false,
-        py::arg("gpu_huf") = false, py::arg("gpu_lz4") = false);
+        py::arg("gpu_huf") = false, py::arg("gpu_lz4") = false,
+        py::arg("gpu_strings") = false);
   // the one descriptor column python looks at (fast-path eligibility)
   m.attr("UD_PRESENT") = (int)UD_PRESENT;
   // where a column's regions lie, and its GPU-decoded value encoding
@@ -914,9 +919,90 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("UD_ENC_OFF") = (int)UD_ENC_OFF;
   m.attr("UD_ENC_CNT") = (int)UD_ENC_CNT;
   m.attr("UD_ENC_PAGES") = (int)UD_ENC_PAGES;
+  m.attr("UD_IS_DICT") = (int)UD_IS_DICT;
+  m.attr("UD_DICT_OFF") = (int)UD_DICT_OFF;
+  m.attr("UD_DICT_LEN") = (int)UD_DICT_LEN;
+  m.attr("UD_RUN_OFF") = (int)UD_RUN_OFF;
+  m.attr("UD_RUN_CNT") = (int)UD_RUN_CNT;
+  m.attr("UD_DENSE_N") = (int)UD_DENSE_N;
+  m.attr("UD_STR") = (int)UD_STR;
+  m.attr("UD_STR_PLAIN") = (int)UD_STR_PLAIN;
+  m.attr("UD_STR_DICT") = (int)UD_STR_DICT;
   m.attr("UD_ENC_DELTA_BINARY") = (int)ParquetFile::ENCK_DELTA_BINARY;
   m.attr("UD_ENC_BYTE_STREAM_SPLIT") = (int)ParquetFile::ENCK_BYTE_STREAM_SPLIT;
   m.def("read_chunks_raw_batch", &read_chunks_raw_batch);
+  // GPU string route: the host twins of _hip.strip_prefixes / dict_strings
+  // (str_seg.h) and the two prefix walks (str_walk.h)
+  m.def("strip_prefixes", [](torch::Tensor raw, torch::Tensor doff) {
+    TORCH_CHECK(raw.is_cpu() && raw.scalar_type() == torch::kUInt8 &&
+                    raw.dim() == 1 && raw.is_contiguous() && doff.is_cpu() &&
+                    doff.scalar_type() == torch::kInt64 && doff.dim() == 1 &&
+                    doff.is_contiguous(),
+                "strip_prefixes: raw uint8 and dense offsets int64, 1-d, on the host");
+    int64_t n = doff.numel() ? doff.numel() - 1 : 0;
+    auto out = lsseg::strip_prefixes_host(
+        raw.numel() ? raw.data_ptr<uint8_t>() : nullptr, raw.numel(),
+        doff.numel() ? doff.data_ptr<int64_t>() : nullptr, n);
+    return vec_to_tensor_u8(std::move(out));
+  });
+  m.def("dict_strings", [](torch::Tensor idx, torch::Tensor dict_off,
+                           torch::Tensor dict_bytes,
+                           c10::optional<torch::Tensor> validity) {
+    TORCH_CHECK(idx.is_cpu() && idx.scalar_type() == torch::kInt32 &&
+                    idx.is_contiguous() && dict_off.is_cpu() &&
+                    dict_off.scalar_type() == torch::kInt64 &&
+                    dict_off.is_contiguous() && dict_off.numel() >= 1 &&
+                    dict_bytes.is_cpu() &&
+                    dict_bytes.scalar_type() == torch::kUInt8 &&
+                    dict_bytes.is_contiguous(),
+                "dict_strings: idx int32, dict_offsets int64 (entries + 1), "
+                "dict_bytes uint8, on the host");
+    const uint8_t* vp = nullptr;
+    int64_t nrows = idx.numel();
+    if (validity.has_value()) {
+      TORCH_CHECK(validity->is_cpu() && validity->scalar_type() == torch::kUInt8 &&
+                      validity->is_contiguous(),
+                  "dict_strings: validity uint8 on the host");
+      nrows = validity->numel();
+      vp = nrows ? validity->data_ptr<uint8_t>() : nullptr;
+      if (!vp) validity.reset();
+    }
+    std::vector<int64_t> offs;
+    std::vector<uint8_t> bytes;
+    int32_t st = lsseg::dict_strings_host(
+        idx.numel() ? idx.data_ptr<int32_t>() : nullptr, idx.numel(),
+        dict_off.data_ptr<int64_t>(), dict_off.numel() - 1,
+        dict_bytes.numel() ? dict_bytes.data_ptr<uint8_t>() : nullptr,
+        dict_bytes.numel(), vp, nrows, offs, bytes);
+    auto ot = torch::empty({(int64_t)offs.size()}, torch::kInt64);
+    std::memcpy(ot.data_ptr(), offs.data(), offs.size() * 8);
+    auto stt = torch::full({1}, (int64_t)st, torch::kInt32);
+    return py::make_tuple(ot, vec_to_tensor_u8(std::move(bytes)), stt);
+  }, py::arg("idx"), py::arg("dict_offsets"), py::arg("dict_bytes"),
+     py::arg("validity") = py::none());
+  m.def("str_walk_plain", [](py::bytes src, int64_t expect) {
+    std::string b = src;
+    std::unique_ptr<uint8_t[]> in(new uint8_t[b.size() ? b.size() : 1]);
+    std::memcpy(in.get(), b.data(), b.size());
+    std::vector<int64_t> offs{0};
+    int64_t total = 0;
+    str_walk_plain(in.get(), b.size(), expect, total, offs);
+    auto ot = torch::empty({(int64_t)offs.size()}, torch::kInt64);
+    std::memcpy(ot.data_ptr(), offs.data(), offs.size() * 8);
+    return ot;
+  });
+  m.def("str_walk_dict", [](py::bytes src, int64_t nent) {
+    std::string b = src;
+    std::unique_ptr<uint8_t[]> in(new uint8_t[b.size() ? b.size() : 1]);
+    std::memcpy(in.get(), b.data(), b.size());
+    std::vector<int64_t> offs{0};
+    std::vector<uint8_t> bytes;
+    int64_t total = 0;
+    str_walk_dict(in.get(), b.size(), nent, total, offs, bytes);
+    auto ot = torch::empty({(int64_t)offs.size()}, torch::kInt64);
+    std::memcpy(ot.data_ptr(), offs.data(), offs.size() * 8);
+    return py::make_tuple(ot, vec_to_tensor_u8(std::move(bytes)));
+  });
   m.def("zstd_compress_ref", [](py::bytes src, int64_t level) {
     std::string b = src;
     auto out = zstd_compress((const uint8_t*)b.data(), b.size(), (int)level);

@@ -36,6 +36,28 @@
 //             dense offsets count stored (non-null) values across the
 //             column's chunks. Every row comes from delta_walk (delta.h):
 //             its span is validated against the page before it is listed.
+//
+// GPU string route (gpu_strings; UD_STR != 0, chosen per (file, column)):
+// the host reads length prefixes only and the GPU moves the bytes
+// (csrc/hip/strings.hip). The decoded column is the same (offsets, compact
+// bytes, validity) triple as on the host route. A column takes a kind only
+// when every chunk of it in the file is of that kind; mixed columns, lists
+// and nested leaves stay host-assembled (UD_STR = 0).
+//   UD_STR_PLAIN: values holds the chunks' decompressed PLAIN streams
+//             (u32 len, bytes)* back to back, unpadded, at UD_VAL_OFF /
+//             UD_VAL_LEN. soffs holds the DENSE offsets (UD_DENSE_N + 1
+//             entries from 0: running sum of the lengths of the stored,
+//             non-null values), so dense value i sits at
+//             val_off + doff[i] + 4 * (i + 1). UD_SBYTES_LEN is the compact
+//             byte total, UD_SBYTES_OFF = -1.
+//   UD_STR_DICT: values and runs hold the RLE index pages as for a
+//             fixed-width dictionary column (run bias = entries of the
+//             column's earlier chunks). dicts holds the entry bytes of all
+//             chunks stripped of their prefixes (UD_DICT_OFF / UD_DICT_LEN),
+//             soffs one table of entry offsets (entries + 1, from 0;
+//             entries = UD_SBYTES_LEN, UD_SBYTES_OFF = -1). RLE run values
+//             are checked against the chunk's dictionary here; bit-packed
+//             indices are checked by the kernel.
 #pragma once
 
 #include <atomic>
@@ -52,7 +74,9 @@
 #include "delta.h"
 #include "parquet_file.h"
 #include "rle.h"
+#include "str_walk.h"
 #include "thread_pool.h"
+#include "unit_desc.h"
 
 namespace lakesoul {
 
@@ -123,6 +147,7 @@ struct UnitColumn {
   int64_t enc_off = 0, enc_cnt = 0, enc_pages = 0;  // rows of UnitStage::enc
   int64_t soff_off = -1;
   int64_t sbytes_off = 0, sbytes_len = 0;
+  int32_t str_kind = UD_STR_HOST;  // GPU string route, see the layout comment
   bool is_list = false;  // element values in the sbytes region, element
                          // offsets in soffs, ROW validity in validity
 };
@@ -174,7 +199,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     const std::vector<std::string>& paths, const std::vector<std::string>& names,
     bool gpu_snappy = false, bool gpu_zstd = false,
     double gpu_zstd_frac = 1.0, bool gpu_delta = false, bool gpu_huf = false,
-    bool gpu_lz4 = false) {
+    bool gpu_lz4 = false, bool gpu_strings = false) {
   auto st = std::make_unique<UnitStage>();
   UnitStage& S = *st;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -255,7 +280,10 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
   // likewise a column is dictionary-decoded only when all of its chunks
   // are: next to a plain chunk (a row group that fell back, or was
   // host-decoded above) the dictionary chunks turn plain on the host
-  for (auto& fd : S.files) {
+  // (such a column is marked: it stays off the GPU string route)
+  std::vector<char> mixed_dict(nfiles * names.size(), 0);
+  for (size_t fi = 0; fi < nfiles; fi++) {
+    auto& fd = S.files[fi];
     for (size_t c = 0; c < names.size(); c++) {
       if (fd.col_idx[c] < 0 || fd.f->columns()[fd.col_idx[c]].is_list) continue;
       bool any_dict = false, any_plain = false;
@@ -264,6 +292,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         else if (ch.num_values > ch.null_count) any_plain = true;
       }
       if (!(any_dict && any_plain)) continue;
+      mixed_dict[fi * names.size() + c] = 1;
       for (auto& ch : fd.chunks[c])
         if (ch.is_dict) ParquetFile::undict_chunk(ch);
     }
@@ -273,6 +302,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
   S.t_chunks_us = us(tp1, tp2);
 
   // layout
+  S.str_cols.resize(nfiles * names.size());
   int64_t vpos = 0, vapos = 0, dpos = 0, spos = 0;
   int64_t huf_comp = 0;  // bytes of Huffman-only frames and LZ4 blocks so far
   for (size_t fi = 0; fi < nfiles; fi++) {
@@ -384,6 +414,71 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         S.enc.insert(S.enc.end(), pages.begin(), pages.end());
         S.enc.insert(S.enc.end(), mbs.begin(), mbs.end());
         uc.enc_cnt = (int64_t)S.enc.size() / 6 - uc.enc_off;
+      } else if (uc.is_string && gpu_strings && cd.max_def <= 1 &&
+                 cd.physical == PT_BYTE_ARRAY &&
+                 cd.name.find('.') == std::string::npos &&
+                 !mixed_dict[fi * names.size() + c]) {
+        // GPU string route (after the fix-up above the chunks with stored
+        // values are all dictionary chunks or all plain ones)
+        uc.soff_off = spos;
+        uc.sbytes_off = -1;
+        int64_t dense = 0;
+        for (auto& ch : chs) dense += ch.num_values - ch.null_count;
+        uc.dense_n = dense;
+        if (!uc.is_dict) {
+          // the walk of the prefixes runs in the pre-pass below
+          uc.str_kind = UD_STR_PLAIN;
+          uc.val_off = vpos;
+          int64_t plen = 0;
+          for (auto& ch : chs) plen += (int64_t)ch.values.size();
+          uc.val_len = plen;
+          vpos += ru_align8(plen);
+          spos += dense + 1;
+        } else {
+          uc.str_kind = UD_STR_DICT;
+          uc.val_off = vpos;
+          auto sd = std::make_unique<UnitStage::StrDecoded>();
+          sd->offs.push_back(0);
+          uc.run_off = (int64_t)S.runs.size() / 6;
+          int64_t poff = uc.val_off, dense_off = 0, bias = 0, dbytes = 0;
+          for (auto& ch : chs) {
+            if (ch.is_dict)
+              str_walk_dict(ch.dict.data(), ch.dict.size(), ch.dict_num_values,
+                            dbytes, sd->offs, sd->bytes);
+            for (auto& ip : ch.idx_pages) {
+              std::vector<RleRun> rr;
+              parse_rle_runs(ch.values.data() + ip.payload_off,
+                             (size_t)ip.payload_len, ip.bit_width, ip.n,
+                             (poff + ip.payload_off) * 8, rr);
+              for (auto& r : rr) {
+                if (!r.is_literal && r.n > 0 &&
+                    (int64_t)r.value >= ch.dict_num_values)
+                  throw std::runtime_error("dictionary index out of range");
+                S.runs.push_back(r.out_off + dense_off);
+                S.runs.push_back(r.n);
+                S.runs.push_back(r.is_literal);
+                S.runs.push_back(r.is_literal ? r.bit_off : (int64_t)r.value + bias);
+                S.runs.push_back(ip.bit_width);
+                S.runs.push_back(bias);
+              }
+              dense_off += ip.n;
+            }
+            poff += ru_align8((int64_t)ch.values.size());
+            if (ch.is_dict) bias += ch.dict_num_values;
+          }
+          if (dense_off != dense)
+            throw std::runtime_error(
+                "dictionary index pages hold another count than the chunks");
+          uc.val_len = poff - uc.val_off + 8;
+          vpos += uc.val_len;
+          uc.run_cnt = (int64_t)S.runs.size() / 6 - uc.run_off;
+          uc.dict_off = dpos;
+          uc.dict_len = (int64_t)sd->bytes.size();
+          dpos += ru_align8(uc.dict_len);
+          uc.sbytes_len = (int64_t)sd->offs.size() - 1;  // entries
+          spos += (int64_t)sd->offs.size();
+          S.str_cols[fi * names.size() + c] = std::move(sd);
+        }
       } else if (uc.is_string) {
         uc.soff_off = spos;
         spos += nv + 1;
@@ -478,11 +573,11 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
   }
 
   // string pre-pass (decode to learn byte totals) — parallel per column
-  S.str_cols.resize(S.cols.size());
   {
     std::vector<size_t> str_idx;
     for (size_t u = 0; u < S.cols.size(); u++)
-      if (S.cols[u].present && (S.cols[u].is_string || S.cols[u].is_list))
+      if (S.cols[u].present && (S.cols[u].is_string || S.cols[u].is_list) &&
+          S.cols[u].str_kind != UD_STR_DICT)
         str_idx.push_back(u);
     std::string err;
     std::mutex err_mu;
@@ -493,7 +588,14 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
         auto& fd = S.files[uc.file_idx];
         auto sd = std::make_unique<UnitStage::StrDecoded>();
         sd->offs.push_back(0);
-        if (uc.is_list) {
+        if (uc.str_kind == UD_STR_PLAIN) {
+          // prefixes only: the payload is not touched on the host
+          int64_t total = 0;
+          sd->offs.reserve((size_t)uc.dense_n + 1);
+          for (auto& ch : fd.chunks[u % S.ncols])
+            str_walk_plain(ch.values.data(), ch.values.size(),
+                           ch.num_values - ch.null_count, total, sd->offs);
+        } else if (uc.is_list) {
           int es = physical_elem_size(uc.physical);
           for (auto& ch : fd.chunks[u % S.ncols]) {
             DecodedColumn dc = decode_chunk_cpu(ch);
@@ -528,6 +630,10 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     if (!err.empty()) throw std::runtime_error(err);
     for (size_t u : str_idx) {
       UnitColumn& uc = S.cols[u];
+      if (uc.str_kind == UD_STR_PLAIN) {
+        uc.sbytes_len = S.str_cols[u]->offs.back();
+        continue;
+      }
       uc.sbytes_off = vpos;
       uc.sbytes_len = (int64_t)S.str_cols[u]->bytes.size();
       vpos += ru_align8(uc.sbytes_len);
@@ -586,6 +692,20 @@ inline void read_unit_fill(UnitStage& S, uint8_t* values, uint8_t* validity,
           std::memcpy(validity + off, ch.validity.data(), ch.validity.size());
         off += ch.num_values;
       }
+    }
+    if (uc.str_kind != UD_STR_HOST) {
+      auto& sd = *S.str_cols[u];
+      std::memcpy(soffs + uc.soff_off, sd.offs.data(), sd.offs.size() * 8);
+      int64_t poff = uc.val_off;
+      for (auto& ch : chs) {
+        if (!ch.values.empty())
+          std::memcpy(values + poff, ch.values.data(), ch.values.size());
+        poff += uc.str_kind == UD_STR_PLAIN ? (int64_t)ch.values.size()
+                                            : ru_align8((int64_t)ch.values.size());
+      }
+      if (!sd.bytes.empty())
+        std::memcpy(dicts + uc.dict_off, sd.bytes.data(), sd.bytes.size());
+      return;
     }
     if (uc.is_string || uc.is_list) {
       auto& sd = *S.str_cols[u];

@@ -28,5 +28,10 @@ enum UnitDescField {
   UD_ENC_OFF,    // first row of the column in the enc table
   UD_ENC_CNT,    // its rows: page rows, then miniblock rows
   UD_ENC_PAGES,  // how many of them are page rows
+  // string column whose bytes the GPU moves (read_unit.h, "GPU string
+  // route"): 0 = host-assembled, UD_STR_PLAIN, UD_STR_DICT
+  UD_STR,
   UD_NFIELDS
 };
+
+enum UnitStrKind { UD_STR_HOST = 0, UD_STR_PLAIN = 1, UD_STR_DICT = 2 };

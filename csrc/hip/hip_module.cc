@@ -5,6 +5,8 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <atomic>
+
 #include "../cpp/unit_desc.h"
 #include "kernels.h"
 
@@ -352,6 +354,123 @@ static std::vector<torch::Tensor> snappy_decompress(torch::Tensor src,
   return {dst, status};
 }
 
+// ---- string columns moved on the GPU (strings.hip) --------------------- //
+
+// Read-backs of dictionary string byte totals by the unit decoder: one per
+// unit that has such columns, however many (the sync-budget test reads it).
+static std::atomic<int64_t> g_dict_total_readbacks{0};
+
+// PLAIN stream `raw` + dense offsets (n + 1, device) -> `out` (total bytes)
+static void strip_prefixes_into(const torch::Tensor& raw, const torch::Tensor& doff,
+                                torch::Tensor& out) {
+  int64_t n = doff.numel() - 1, total = out.numel();
+  if (total == 0 || n <= 0) return;
+  launch_strip_prefixes(raw.data_ptr<uint8_t>(), raw.numel(),
+                        doff.data_ptr<int64_t>(), n, out.data_ptr<uint8_t>(),
+                        total, cur_stream());
+}
+
+// direct binding: one host sync, at the byte total. `out`, when given, is
+// where the bytes go (any alignment); it must hold exactly the total.
+static torch::Tensor strip_prefixes(torch::Tensor raw, torch::Tensor doff,
+                                    c10::optional<torch::Tensor> out) {
+  CHECK_GPU_NONEMPTY(raw);
+  CHECK_GPU_NONEMPTY(doff);
+  TORCH_CHECK(raw.scalar_type() == torch::kUInt8 && raw.dim() == 1 &&
+                  doff.scalar_type() == torch::kInt64 && doff.dim() == 1,
+              "strip_prefixes: raw uint8 and dense offsets int64, 1-d");
+  auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(
+      doff.numel() ? doff.device() : raw.device());
+  int64_t n = doff.numel() ? doff.numel() - 1 : 0;
+  int64_t total = n > 0 ? doff[n].item<int64_t>() : 0;
+  TORCH_CHECK(total >= 0 && total + 4 * n <= raw.numel(),
+              "strip_prefixes: offsets past the raw stream");
+  torch::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    TORCH_CHECK(o.numel() == 0 || (o.is_cuda() && o.is_contiguous()),
+                "strip_prefixes: out must be a contiguous GPU tensor");
+    TORCH_CHECK(o.scalar_type() == torch::kUInt8 && o.numel() == total,
+                "strip_prefixes: out must hold exactly ", total, " bytes");
+  } else {
+    o = torch::empty({total}, u8);
+  }
+  if (total) strip_prefixes_into(raw, doff, o);
+  return o;
+}
+
+// A dictionary string column, first half: row offsets from the dense
+// indices. status: int32 [1] device, or-ed into.
+struct DictStr {
+  torch::Tensor offsets, entry, dict_off, dict_bytes;
+  int64_t nrows = 0;
+};
+
+static DictStr dict_str_offsets(const torch::Tensor& idx, const torch::Tensor& dict_off,
+                                const torch::Tensor& dict_bytes,
+                                const torch::Tensor& vmask, int64_t nrows,
+                                torch::Tensor status) {
+  DictStr ds;
+  ds.nrows = nrows;
+  ds.dict_off = dict_off;
+  ds.dict_bytes = dict_bytes;
+  auto i64 = dict_off.options().dtype(torch::kInt64);
+  ds.offsets = torch::zeros({nrows + 1}, i64);
+  ds.entry = torch::empty({nrows}, i64.dtype(torch::kInt32));
+  if (nrows == 0) return ds;
+  auto lens = torch::empty({nrows}, i64);
+  torch::Tensor pos;
+  if (vmask.defined()) pos = at::cumsum(vmask, 0, torch::kInt64) - 1;
+  launch_dict_str_lens(idx.numel() ? idx.data_ptr<int32_t>() : nullptr, idx.numel(),
+                       dict_off.data_ptr<int64_t>(), dict_off.numel() - 1,
+                       vmask.defined() ? vmask.data_ptr<uint8_t>() : nullptr,
+                       vmask.defined() ? pos.data_ptr<int64_t>() : nullptr, nrows,
+                       lens.data_ptr<int64_t>(), ds.entry.data_ptr<int32_t>(),
+                       status.data_ptr<int32_t>(), cur_stream());
+  ds.offsets.narrow(0, 1, nrows).copy_(at::cumsum(lens, 0));
+  return ds;
+}
+
+// second half, once the byte total is on the host
+static torch::Tensor dict_str_bytes(const DictStr& ds, int64_t total) {
+  auto out = torch::empty({total}, ds.dict_off.options().dtype(torch::kUInt8));
+  if (total > 0)
+    launch_dict_str_copy(opt_u8(ds.dict_bytes), ds.dict_bytes.numel(),
+                         ds.dict_off.data_ptr<int64_t>(), ds.dict_off.numel() - 1,
+                         ds.entry.data_ptr<int32_t>(),
+                         ds.offsets.data_ptr<int64_t>(), ds.nrows,
+                         out.data_ptr<uint8_t>(), total, cur_stream());
+  return out;
+}
+
+// direct binding: dense idx (one per valid row) -> (row offsets, bytes,
+// status int32 [1]); rows whose index is no entry are empty and set status
+static std::vector<torch::Tensor> dict_strings(torch::Tensor idx, torch::Tensor dict_off,
+                                               torch::Tensor dict_bytes,
+                                               c10::optional<torch::Tensor> validity) {
+  CHECK_GPU_NONEMPTY(idx);
+  CHECK_GPU_NONEMPTY(dict_bytes);
+  CHECK_GPU(dict_off);
+  TORCH_CHECK(idx.scalar_type() == torch::kInt32 &&
+                  dict_off.scalar_type() == torch::kInt64 && dict_off.numel() >= 1 &&
+                  dict_bytes.scalar_type() == torch::kUInt8,
+              "dict_strings: idx int32, dict_offsets int64 (entries + 1), dict_bytes uint8");
+  torch::Tensor vmask;
+  int64_t nrows = idx.numel();
+  if (validity.has_value()) {
+    nrows = validity->numel();
+    if (nrows) {
+      CHECK_GPU(*validity);
+      TORCH_CHECK(validity->scalar_type() == torch::kUInt8, "dict_strings: validity uint8");
+      vmask = *validity;
+    }
+  }
+  auto status = torch::zeros({1}, dict_off.options().dtype(torch::kInt32));
+  auto ds = dict_str_offsets(idx, dict_off, dict_bytes, vmask, nrows, status);
+  int64_t total = nrows ? ds.offsets[nrows].item<int64_t>() : 0;
+  return {ds.offsets, dict_str_bytes(ds, total), status};
+}
+
 // ---------------------------------------------------------------------- //
 // Scan-unit decode: every (file, column) chunk of one unit into dense
 // device columns. desc: int64 [nfiles*ncols, UD_NFIELDS] from
@@ -389,6 +508,17 @@ static std::vector<UnitCol> decode_unit_cols(
               "decode_unit: enc must be an int64 [m, 6] tensor");
   const int64_t enc_rows = enc.numel() / 6;
 
+  // dictionary string columns (UD_STR_DICT): their byte totals are known
+  // only on the device. Every column's offsets are computed in the loop
+  // below; the totals and statuses then come back in ONE copy for the whole
+  // unit, and the bytes move after it.
+  int64_t n_dict_str = 0;
+  for (int64_t u = 0; u < nfiles * ncols; u++)
+    if (da[u][UD_PRESENT] && da[u][UD_STR] == UD_STR_DICT) n_dict_str++;
+  torch::Tensor dict_status;
+  if (n_dict_str) dict_status = torch::zeros({n_dict_str}, u8.dtype(torch::kInt32));
+  std::vector<std::pair<int64_t, DictStr>> dict_strs;
+
   std::vector<UnitCol> cols((size_t)(nfiles * ncols));
   for (int64_t u = 0; u < nfiles * ncols; u++) {
     UnitCol& out = cols[(size_t)u];
@@ -399,6 +529,57 @@ static std::vector<UnitCol> decode_unit_cols(
     bool has_null = d[UD_VALIDITY_OFF] >= 0 && d[UD_NULL_COUNT] > 0;
     if (has_null) out.validity = validity_buf.narrow(0, d[UD_VALIDITY_OFF], nv);
     const torch::Tensor& vmask = out.validity;
+    if (d[UD_STR]) {
+      // GPU string route: the host shipped prefixes / indices, the bytes
+      // move here (strings.hip)
+      TORCH_CHECK(d[UD_IS_STRING] && !d[UD_IS_LIST], "decode_unit: UD_STR on a non-string column");
+      out.is_string = true;
+      int64_t dn = d[UD_DENSE_N];
+      TORCH_CHECK(dn >= 0 && dn <= nv && (has_null || dn == nv),
+                  "decode_unit: bad dense count of a string column");
+      TORCH_CHECK(d[UD_VAL_OFF] >= 0 && d[UD_VAL_LEN] >= 0 &&
+                      d[UD_VAL_OFF] + d[UD_VAL_LEN] <= vals.numel(),
+                  "decode_unit: string payload out of range");
+      if (d[UD_STR] == UD_STR_PLAIN) {
+        int64_t total = d[UD_SBYTES_LEN];
+        TORCH_CHECK(d[UD_SOFF_OFF] >= 0 && d[UD_SOFF_OFF] + dn + 1 <= soffs.numel() &&
+                        total >= 0 && total + 4 * dn == d[UD_VAL_LEN],
+                    "decode_unit: string offsets out of range");
+        auto doff = soffs.narrow(0, d[UD_SOFF_OFF], dn + 1);
+        out.bytes = torch::empty({total}, u8);
+        strip_prefixes_into(vals.narrow(0, d[UD_VAL_OFF], d[UD_VAL_LEN]), doff, out.bytes);
+        if (has_null) {
+          // row r starts where the dense value after its earlier valid rows does
+          auto pos = at::clamp_max(
+              at::cumsum(vmask, 0, torch::kInt64) - vmask.to(torch::kInt64), dn);
+          out.offsets = at::cat({doff.index({pos}), doff.narrow(0, dn, 1)});
+        } else {
+          out.offsets = doff;
+        }
+      } else {
+        TORCH_CHECK(d[UD_STR] == UD_STR_DICT, "decode_unit: unknown string tag ", d[UD_STR]);
+        int64_t nent = d[UD_SBYTES_LEN];
+        TORCH_CHECK(nent >= 0 && d[UD_SOFF_OFF] >= 0 &&
+                        d[UD_SOFF_OFF] + nent + 1 <= soffs.numel() &&
+                        d[UD_DICT_OFF] >= 0 && d[UD_DICT_LEN] >= 0 &&
+                        d[UD_DICT_OFF] + d[UD_DICT_LEN] <= dicts.numel() &&
+                        d[UD_RUN_OFF] >= 0 && d[UD_RUN_CNT] >= 0 &&
+                        d[UD_RUN_OFF] + d[UD_RUN_CNT] <= runs.numel() / 6,
+                    "decode_unit: string dictionary out of range");
+        auto idx = torch::empty({dn}, u8.dtype(torch::kInt32));
+        if (d[UD_RUN_CNT]) {
+          auto rr = runs2.narrow(0, d[UD_RUN_OFF], d[UD_RUN_CNT]);
+          launch_rle_expand(vals.data_ptr<uint8_t>(), rr.data_ptr<int64_t>(),
+                            rr.size(0), idx.data_ptr<int32_t>(), dn, stream);
+        }
+        int64_t k = (int64_t)dict_strs.size();
+        dict_strs.emplace_back(u, dict_str_offsets(
+            idx, soffs.narrow(0, d[UD_SOFF_OFF], nent + 1),
+            dicts.numel() ? dicts.narrow(0, d[UD_DICT_OFF], d[UD_DICT_LEN]) : dicts,
+            vmask, nv, dict_status.narrow(0, k, 1)));
+      }
+      continue;
+    }
     if (d[UD_IS_STRING] || d[UD_IS_LIST]) {
       out.is_string = d[UD_IS_STRING];
       out.is_list = d[UD_IS_LIST];
@@ -484,6 +665,24 @@ static std::vector<UnitCol> decode_unit_cols(
       } else {
         out.data = dense;
       }
+    }
+  }
+  if (!dict_strs.empty()) {
+    std::vector<torch::Tensor> parts;
+    for (auto& [u, ds] : dict_strs) parts.push_back(ds.offsets.narrow(0, ds.nrows, 1));
+    parts.push_back(dict_status.to(torch::kInt64));
+    auto host = at::cat(parts).cpu();  // the unit's one sync for these columns
+    g_dict_total_readbacks++;
+    const int64_t* h = host.data_ptr<int64_t>();
+    const int64_t k = (int64_t)dict_strs.size();
+    for (int64_t i = 0; i < k; i++)
+      TORCH_CHECK(h[k + i] == 0,
+                  "GPU dictionary string decode: index out of range (status ",
+                  h[k + i], ", unit column ", dict_strs[(size_t)i].first, ")");
+    for (int64_t i = 0; i < k; i++) {
+      UnitCol& out = cols[(size_t)dict_strs[(size_t)i].first];
+      out.offsets = dict_strs[(size_t)i].second.offsets;
+      out.bytes = dict_str_bytes(dict_strs[(size_t)i].second, h[i]);
     }
   }
   return cols;
@@ -860,6 +1059,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                  C, nq, wn, (int)dim, cur_stream());
     return out;
   });
+  m.def("strip_prefixes", &strip_prefixes, py::arg("raw"), py::arg("dense_offsets"),
+        py::arg("out") = py::none());
+  m.def("dict_strings", &dict_strings, py::arg("idx"), py::arg("dict_offsets"),
+        py::arg("dict_bytes"), py::arg("validity") = py::none());
+  m.def("dict_total_readbacks", []() { return g_dict_total_readbacks.load(); },
+        "read-backs of dictionary string byte totals by the unit decoder so far");
   m.def("snappy_decompress", &snappy_decompress);
   m.def("snappy_decompress_into", &snappy_decompress_into);
   m.def("lz4_decompress", &lz4_decompress);

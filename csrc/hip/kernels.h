@@ -110,6 +110,28 @@ void launch_byte_stream_split(const uint8_t* payload, int64_t vals_len,
                               const int64_t* pages, int64_t npages, T* out,
                               int64_t dense_n, hipStream_t s);
 
+// strings.hip — byte-parallel segment copy of string columns (the GPU
+// string route of ../cpp/read_unit.h). Offsets tables hold one more entry
+// than values / rows / entries and start at 0; `dst` holds `total` bytes.
+// Every source read is checked against raw_len / dict_len.
+void launch_strip_prefixes(const uint8_t* raw, int64_t raw_len,
+                           const int64_t* dense_off, int64_t n, uint8_t* dst,
+                           int64_t total, hipStream_t s);
+// per row: value length and dictionary entry (-1: null row or bad index);
+// pos[r] = dense index of valid row r (read only with a validity);
+// *status gets bit 0 for an index that is no entry, bit 1 for a valid row
+// with no stored index
+void launch_dict_str_lens(const int32_t* idx, int64_t n_idx,
+                          const int64_t* dict_off, int64_t nent,
+                          const uint8_t* validity, const int64_t* pos,
+                          int64_t nrows, int64_t* lens, int32_t* entry,
+                          int32_t* status, hipStream_t s);
+void launch_dict_str_copy(const uint8_t* dict_bytes, int64_t dict_len,
+                          const int64_t* dict_off, int64_t nent,
+                          const int32_t* entry, const int64_t* row_off,
+                          int64_t nrows, uint8_t* dst, int64_t total,
+                          hipStream_t s);
+
 // snappy.hip, lz4.hip, zstd.hip, zstd_huf.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,

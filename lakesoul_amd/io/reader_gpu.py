@@ -13,8 +13,14 @@ Pipeline per scan unit:
    kernels; nullable PLAIN columns scatter through validity;
 4. GPU merge-on-read (merge_gpu) with the merge-path kernel.
 
-String columns are host-assembled ((len,bytes) stream is serial) and ship
-as (offsets int64, bytes) into HBM.
+String columns whose chunks in a file are all PLAIN or all dictionary-coded
+ship raw: the host only walks the length prefixes (PLAIN) or the dictionary
+page (dictionary), and csrc/hip/strings.hip moves the bytes in HBM, a
+byte-parallel segment copy (read_unit.h, UD_STR). Mixed columns, lists and
+nested leaves, and every string column under LAKESOUL_GPU_STRINGS=0, are
+host-assembled ((len,bytes) stream is serial) and ship as (offsets int64,
+bytes). The decoded (offsets, bytes, validity) triple is the same on both
+routes.
 """
 
 from __future__ import annotations
@@ -108,13 +114,27 @@ _GPU_HUF = _os.environ.get("LAKESOUL_GPU_HUF", "1") != "0"
 _GPU_LZ4 = _os.environ.get("LAKESOUL_GPU_LZ4", "0") == "1"
 
 
+# String columns whose chunks are all PLAIN (or all dictionary-encoded):
+# ship the raw streams and let the GPU strip the prefixes / expand the
+# dictionary (csrc/hip/strings.hip) instead of assembling the bytes on the
+# host. Mixed columns, lists and nested leaves stay host-assembled.
+# On by default for both kinds; LAKESOUL_GPU_STRINGS=0 forces the host
+# route. Measured on single-column unit reads (benchmarks/string_micro.py,
+# profiles/r05_gpu_strings.md): a 7-value dictionary column of 8 M rows
+# 159 ms -> 2.4 ms (3.8 MB over the bus instead of 103 MB), 40-byte PLAIN
+# keys 424 ms -> 130 ms, 1 KB PLAIN values 1351 ms -> 805 ms, each gap
+# larger than the run-to-run spread; the headline scan (no string column)
+# is unchanged.
+_GPU_STRINGS = _os.environ.get("LAKESOUL_GPU_STRINGS", "1") != "0"
+
+
 def fetch_raw(files: List[str], names: List[str]) -> dict:
     """Host phase of a unit read (releases the GIL in C++) — safe to run
     on a prefetch thread while the GPU processes the previous unit."""
     with timing.phase("host_fetch"):
         raw = cpp().read_unit_raw(files, names, 0, True, True, _GPU_ZSTD,
                                   _GPU_ZSTD_FRAC, _GPU_DELTA, _GPU_HUF,
-                                  _GPU_LZ4)
+                                  _GPU_LZ4, _GPU_STRINGS)
     if timing.ENABLED:
         timing._acc["fetch.stage1"] += raw["t_stage1_us"] / 1e6
         timing._acc["fetch.s1_open"] += raw["t_open_us"] / 1e6

@@ -49,6 +49,7 @@ if _WITH_HIP:
                 os.path.join("csrc", "hip", "zstd.hip"),
                 os.path.join("csrc", "hip", "zstd_huf.hip"),
                 os.path.join("csrc", "hip", "delta.hip"),
+                os.path.join("csrc", "hip", "strings.hip"),
             ],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
