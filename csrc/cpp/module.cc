@@ -11,6 +11,7 @@
 #include <unordered_map>
 #include <chrono>
 
+#include "merge_plan.h"
 #include "murmur3.h"
 #include "parquet_file.h"
 #include "read_unit.h"
@@ -1148,4 +1149,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return (int64_t)spark_hash_bytes((const uint8_t*)s.data(), (int64_t)s.size(),
                                      (uint32_t)seed);
   });
+  // the batched-merge plan (merge_plan.h) of streams of these lengths, for
+  // tests: (rounds, nbufs, n, tile_rows). A round is
+  // (pairs, carry_or_None, buf_out, ntiles), a pair (a, b, first_tile,
+  // ntiles), a stream (buf, first, count, off, n).
+  m.def("merge_plan", [](std::vector<int64_t> lens) {
+    auto st = [](const MergeStream& s) {
+      return py::make_tuple(s.buf, s.first, s.count, s.off, s.n);
+    };
+    MergePlan plan = plan_merge(lens);
+    py::list rounds;
+    for (auto& r : plan.rounds) {
+      py::list pairs;
+      for (auto& p : r.pairs)
+        pairs.append(py::make_tuple(st(p.a), st(p.b), p.first_tile, p.ntiles));
+      rounds.append(py::make_tuple(pairs, r.has_carry ? py::object(st(r.carry)) : py::none(),
+                                   r.buf_out, r.ntiles));
+    }
+    return py::make_tuple(rounds, plan.nbufs, plan.n, MERGE_TILE_ROWS);
+  }, py::arg("lens"));
 }

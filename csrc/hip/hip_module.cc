@@ -7,6 +7,7 @@
 
 #include <atomic>
 
+#include "../cpp/merge_plan.h"
 #include "../cpp/unit_desc.h"
 #include "kernels.h"
 
@@ -119,45 +120,135 @@ static void scatter_valid_es(int64_t es, const void* dense, const uint8_t* vmask
 
 // ---- merge ------------------------------------------------------------ //
 
+// K sorted key streams through the batched merge rounds (merge_plan.h,
+// kernels.hip merge_round_kernel): one launch per round and 16 pairs, an
+// odd stream carried forward by pointer; on equal keys the earlier (older)
+// stream comes first. Input streams are int64 or int32 keys (key_format:
+// MERGE_KEY_I64 / _I32, packed in registers) or already packed u64 keys in
+// int64 storage (MERGE_KEY_PACKED). Row values are positions in the
+// concatenation of the streams in input order; those of the inputs are
+// computed, never stored.
+//   keep_last = false: (merged packed keys, row of each merged key)
+//   keep_last = true: (undefined, the row of the LAST of every run of equal
+//     keys, in key order). The last round writes no keys and compacts the
+//     survivors tile by tile; one host sync, at their total.
+static std::pair<torch::Tensor, torch::Tensor> merge_rounds(
+    const std::vector<torch::Tensor>& keys, int key_format, bool keep_last) {
+  auto stream = cur_stream();
+  auto i64 = keys[0].options().dtype(torch::kInt64);
+  std::vector<int64_t> lens;
+  for (auto& k : keys) lens.push_back(k.numel());
+  MergePlan plan = plan_merge(lens);
+  const int64_t n = plan.n;
+  if (keep_last && plan.rounds.empty()) {
+    // one stream: the keep-last round alone, against an empty B
+    MergeRound r;
+    MergePair p;
+    p.a.n = n;
+    p.b.off = n;
+    p.ntiles = (n + MERGE_TILE_ROWS - 1) / MERGE_TILE_ROWS;
+    r.pairs.push_back(p);
+    r.buf_out = MP_RESULT;
+    r.ntiles = p.ntiles;
+    plan.rounds.push_back(r);
+  }
+  torch::Tensor out_keys, out_rows, kbuf, rbuf, counts;
+  if (plan.nbufs) {
+    kbuf = torch::empty({plan.nbufs, n}, i64);
+    rbuf = torch::empty({plan.nbufs, n}, i64);
+  }
+  const int64_t last_tiles = plan.rounds.back().ntiles;
+  if (keep_last) {
+    out_rows = torch::empty({last_tiles * MERGE_TILE_ROWS}, i64);  // tile slots
+    counts = torch::empty({last_tiles}, i64);
+  } else {
+    out_keys = torch::empty({n}, i64);
+    out_rows = torch::empty({n}, i64);
+  }
+  auto set_stream = [&](const MergeStream& s, const void*& k, const int64_t*& r,
+                        int64_t& cnt, int64_t& base) {
+    cnt = s.n;
+    base = s.off;
+    if (s.buf == MP_INPUT) {
+      k = s.n ? keys[(size_t)s.first].data_ptr() : nullptr;
+      r = nullptr;
+    } else {
+      k = kbuf.data_ptr<int64_t>() + s.buf * n + s.off;
+      r = rbuf.data_ptr<int64_t>() + s.buf * n + s.off;
+    }
+  };
+  for (auto& round : plan.rounds) {
+    const bool last = round.buf_out == MP_RESULT;
+    for (size_t c0 = 0; c0 < round.pairs.size(); c0 += MERGE_PAIRS_PER_LAUNCH) {
+      MergeTable tbl;
+      tbl.npairs = 0;
+      tbl.ntiles = 0;
+      tbl.tile_counts = last && keep_last ? counts.data_ptr<int64_t>() : nullptr;
+      for (size_t j = c0; j < round.pairs.size() && tbl.npairs < MERGE_PAIRS_PER_LAUNCH; j++) {
+        const MergePair& p = round.pairs[j];
+        MergePairArg& a = tbl.p[tbl.npairs++];
+        set_stream(p.a, a.kA, a.rA, a.nA, a.baseA);
+        set_stream(p.b, a.kB, a.rB, a.nB, a.baseB);
+        if (last) {
+          a.kOut = keep_last ? nullptr : (uint64_t*)out_keys.data_ptr<int64_t>() + p.a.off;
+          a.rOut = out_rows.data_ptr<int64_t>() + p.a.off;
+        } else {
+          a.kOut = (uint64_t*)kbuf.data_ptr<int64_t>() + round.buf_out * n + p.a.off;
+          a.rOut = rbuf.data_ptr<int64_t>() + round.buf_out * n + p.a.off;
+        }
+        a.first_tile = tbl.ntiles;
+        tbl.ntiles += p.ntiles;
+      }
+      if (last && keep_last)
+        launch_merge_round_keep_last(tbl, key_format, stream);
+      else
+        launch_merge_round(tbl, key_format, stream);
+    }
+  }
+  if (!keep_last) return {out_keys, out_rows};
+  if (last_tiles == 0) return {out_keys, torch::empty({0}, i64)};
+  auto csum = at::cumsum(counts, 0);
+  int64_t kept = csum[last_tiles - 1].item<int64_t>();  // the path's one sync
+  auto src_idx = torch::empty({kept}, i64);
+  launch_compact_tiles(out_rows.data_ptr<int64_t>(), counts.data_ptr<int64_t>(),
+                       csum.data_ptr<int64_t>(), last_tiles,
+                       src_idx.data_ptr<int64_t>(), stream);
+  return {out_keys, src_idx};
+}
+
 // K sorted streams of packed u64 keys (int64 storage) -> (keys, order):
 // the merged keys and, per merged row, its index in the concatenation of
-// the streams in input order. Pairwise merge-path passes, an odd stream
-// carried forward; on equal keys the earlier (older) stream comes first.
+// the streams in input order (the merge_sorted_keys binding).
 static std::pair<torch::Tensor, torch::Tensor> merge_key_streams(
     std::vector<torch::Tensor> keys) {
   TORCH_CHECK(!keys.empty(), "merge_sorted_keys: no streams");
-  std::vector<torch::Tensor> rows;
-  int64_t base = 0;
   for (auto& k : keys) {
     CHECK_GPU(k);
     TORCH_CHECK(k.scalar_type() == torch::kInt64 && k.dim() == 1,
                 "merge_sorted_keys: keys must be 1-d int64");
-    rows.push_back(torch::arange(base, base + k.numel(), k.options()));
-    base += k.numel();
   }
-  auto stream = cur_stream();
-  while (keys.size() > 1) {
-    std::vector<torch::Tensor> nk, nr;
-    for (size_t j = 0; j + 1 < keys.size(); j += 2) {
-      int64_t nA = keys[j].numel(), nB = keys[j + 1].numel();
-      auto kO = torch::empty({nA + nB}, keys[j].options());
-      auto vO = torch::empty({nA + nB}, keys[j].options());
-      if (nA + nB)  // an empty pair would be a grid of 0 blocks
-        launch_merge_pairs(
-            (const uint64_t*)keys[j].data_ptr(), (const uint64_t*)rows[j].data_ptr(), nA,
-            (const uint64_t*)keys[j + 1].data_ptr(), (const uint64_t*)rows[j + 1].data_ptr(), nB,
-            (uint64_t*)kO.data_ptr(), (uint64_t*)vO.data_ptr(), stream);
-      nk.push_back(kO);
-      nr.push_back(vO);
-    }
-    if (keys.size() % 2) {
-      nk.push_back(keys.back());
-      nr.push_back(rows.back());
-    }
-    keys = std::move(nk);
-    rows = std::move(nr);
+  if (keys.size() == 1)
+    return {keys[0], torch::arange(keys[0].numel(), keys[0].options())};
+  return merge_rounds(keys, MERGE_KEY_PACKED, false);
+}
+
+// K sorted streams of raw int64 or int32 keys -> src_idx: for every
+// distinct key, in key order, the position of its LAST row in the
+// concatenation of the streams in input order (later stream wins, inside a
+// stream the later row). The merge of scan_unit_uselast; also the
+// unit_merge_src_idx binding.
+static torch::Tensor unit_merge_src_idx(std::vector<torch::Tensor> keys) {
+  TORCH_CHECK(!keys.empty(), "unit_merge_src_idx: no streams");
+  auto dt = keys[0].scalar_type();
+  TORCH_CHECK(dt == torch::kInt64 || dt == torch::kInt32,
+              "unit_merge_src_idx: keys must be int64 or int32");
+  for (auto& k : keys) {
+    CHECK_GPU(k);
+    TORCH_CHECK(k.scalar_type() == dt && k.dim() == 1,
+                "unit_merge_src_idx: keys must be 1-d and of one dtype");
   }
-  return {keys[0], rows[0]};
+  return merge_rounds(keys, dt == torch::kInt64 ? MERGE_KEY_I64 : MERGE_KEY_I32, true)
+      .second;
 }
 
 static torch::Tensor group_start_mask(torch::Tensor keys) {
@@ -218,6 +309,102 @@ static std::vector<torch::Tensor> gather_fixed(std::vector<torch::Tensor> cols,
     launch_gather_fixed_multi(tbl, idx.data_ptr<int64_t>(), n, cur_stream());
   }
   return outs;
+}
+
+// One column of gather_files: per file its buffer of rows[f] elements of
+// `es` bytes, or nullptr for a file whose value is 1 in every row (a file
+// without validity); dst holds idx.numel() elements.
+struct FileColumn {
+  std::vector<const void*> src;
+  int es;
+  void* dst;
+};
+
+// dst[c][i] = the row idx[i] of column c, where idx counts rows over the
+// files in file order (rows[f] rows in file f): the gather of
+// gather_fixed without a concatenated copy of the column. A launch takes 16
+// columns and 16 files; with more files every 16 take a launch of their
+// own, which writes the rows that fall into them. An idx outside all files
+// leaves its output row unwritten.
+static void gather_files_launch(const std::vector<FileColumn>& cols,
+                                const std::vector<int64_t>& rows,
+                                const torch::Tensor& idx) {
+  const int64_t n = idx.numel();
+  const size_t nfiles = rows.size();
+  std::vector<int64_t> start(nfiles + 1, 0);
+  for (size_t f = 0; f < nfiles; f++) start[f + 1] = start[f] + rows[f];
+  for (size_t c0 = 0; c0 < cols.size(); c0 += GATHER_FILES_MAX_COLS) {
+    for (size_t f0 = 0; f0 < nfiles; f0 += GATHER_FILES_MAX_FILES) {
+      GatherFilesTable tbl = {};
+      tbl.nfiles = (int)std::min<size_t>(GATHER_FILES_MAX_FILES, nfiles - f0);
+      for (int f = 0; f <= tbl.nfiles; f++) tbl.start[f] = start[f0 + f];
+      for (int f = tbl.nfiles; f < GATHER_FILES_MAX_FILES; f++) tbl.start[f + 1] = tbl.start[f];
+      for (size_t c = c0; c < cols.size() && tbl.ncols < GATHER_FILES_MAX_COLS; c++) {
+        const FileColumn& col = cols[c];
+        TORCH_CHECK(col.es == 1 || col.es == 2 || col.es == 4 || col.es == 8,
+                    "gather_files: unsupported elem size ", col.es);
+        for (int f = 0; f < tbl.nfiles; f++) tbl.src[tbl.ncols][f] = col.src[f0 + f];
+        tbl.dst[tbl.ncols] = col.dst;
+        tbl.esize[tbl.ncols] = col.es;
+        tbl.ncols++;
+      }
+      launch_gather_files(tbl, idx.data_ptr<int64_t>(), n, cur_stream());
+    }
+  }
+}
+
+// the gather_files binding: cols[c][f] is file f's part of column c (1-d,
+// rows[f] elements of a 1/2/4/8-byte dtype) or None for a file of ones.
+// Returns one tensor per column; with `outs` given, writes into those.
+static std::vector<torch::Tensor> gather_files(
+    std::vector<std::vector<c10::optional<torch::Tensor>>> cols,
+    std::vector<int64_t> rows, torch::Tensor idx,
+    c10::optional<std::vector<torch::Tensor>> outs) {
+  CHECK_GPU(idx);
+  TORCH_CHECK(idx.scalar_type() == torch::kInt64 && idx.dim() == 1,
+              "gather_files: idx must be 1-d int64");
+  TORCH_CHECK(!outs.has_value() || outs->size() == cols.size(),
+              "gather_files: one output per column");
+  const int64_t n = idx.numel();
+  std::vector<FileColumn> fcs;
+  std::vector<torch::Tensor> res;
+  for (size_t c = 0; c < cols.size(); c++) {
+    TORCH_CHECK(cols[c].size() == rows.size(), "gather_files: one part per file");
+    FileColumn fc;
+    torch::Tensor first;
+    for (size_t f = 0; f < rows.size(); f++) {
+      if (!cols[c][f].has_value()) {
+        fc.src.push_back(nullptr);
+        continue;
+      }
+      const torch::Tensor& t = *cols[c][f];
+      CHECK_GPU(t);
+      if (!first.defined()) first = t;
+      TORCH_CHECK(t.dim() == 1 && t.numel() == rows[f] &&
+                      t.scalar_type() == first.scalar_type(),
+                  "gather_files: a part must be 1-d, of its file's row count "
+                  "and of the column's dtype");
+      fc.src.push_back(t.data_ptr());  // null for an empty part: no row reads it
+    }
+    TORCH_CHECK(first.defined(), "gather_files: a column of no parts");
+    fc.es = (int)first.element_size();
+    torch::Tensor out;
+    if (outs.has_value()) {
+      out = (*outs)[c];
+      CHECK_GPU(out);
+      TORCH_CHECK(out.dim() == 1 && out.numel() == n &&
+                      out.scalar_type() == first.scalar_type(),
+                  "gather_files: an output must be 1-d, of idx's size and of "
+                  "the column's dtype");
+    } else {
+      out = torch::empty({n}, first.options());
+    }
+    fc.dst = out.data_ptr();
+    fcs.push_back(std::move(fc));
+    res.push_back(out);
+  }
+  gather_files_launch(fcs, rows, idx);
+  return res;
 }
 
 // Rows idx of a string column -> (new_offsets, new_bytes). One host sync,
@@ -729,15 +916,13 @@ static py::list decode_unit(torch::Tensor vals, torch::Tensor validity_buf,
   return unit_cols_to_py(cols);
 }
 
-// Each read column of a decoded unit (no absent or list columns)
-// concatenated across its files in file order: one UnitCol per column.
-// Fixed-width data comes back as [rows, es]. Validity is defined when any
-// file has one; files without are filled with ones. String offsets are
-// rebased onto the concatenated bytes.
+// The string columns of a decoded unit (no absent or list columns)
+// concatenated across their files in file order: offsets rebased onto the
+// concatenated bytes. One UnitCol per column; a fixed-width column comes
+// back empty (it is gathered straight from the per-file buffers, as every
+// validity is: gather_files).
 static std::vector<UnitCol> concat_unit_files(const std::vector<UnitCol>& flat,
-                                              const torch::Tensor& desc,
                                               int64_t nfiles, int64_t ncols) {
-  auto da = desc.accessor<int64_t, 2>();
   std::vector<UnitCol> out((size_t)ncols);
   for (int64_t c = 0; c < ncols; c++) {
     auto part = [&](int64_t f) -> const UnitCol& { return flat[(size_t)(f * ncols + c)]; };
@@ -749,19 +934,7 @@ static std::vector<UnitCol> concat_unit_files(const std::vector<UnitCol>& flat,
     UnitCol& o = out[(size_t)c];
     o.present = true;
     o.is_string = part(0).is_string;
-    torch::Tensor a_valid;  // some file's validity, if any has one
-    for (int64_t f = 0; f < nfiles; f++)
-      if (part(f).validity.defined()) a_valid = part(f).validity;
-    if (a_valid.defined())
-      o.validity = cat([&](int64_t f) {
-        auto& v = part(f).validity;
-        return v.defined() ? v : torch::ones({da[f * ncols + c][UD_NUM_VALUES]}, a_valid.options());
-      });
-    if (!o.is_string) {
-      int64_t es = da[c][UD_ESIZE];
-      o.data = cat([&](int64_t f) { return part(f).data.view({-1, es}); });
-      continue;
-    }
+    if (!o.is_string) continue;
     int64_t byte_base = 0;
     o.offsets = cat([&](int64_t f) {
       auto offs = part(f).offsets;
@@ -780,7 +953,7 @@ static std::vector<UnitCol> concat_unit_files(const std::vector<UnitCol>& flat,
 // was the scan's critical path. Covers: integer single-PK (int64/int32),
 // every-column UseLast, no CDC, no lists, no absent columns. Python falls
 // back otherwise. One merged UnitCol per read column. Host syncs: one at
-// nonzero, one per string column at its byte total.
+// the survivor count, one per string column at its byte total.
 static std::vector<UnitCol> scan_unit_uselast_cols(
     const torch::Tensor& vals, const torch::Tensor& validity_buf,
     const torch::Tensor& dicts, const torch::Tensor& runs,
@@ -793,39 +966,63 @@ static std::vector<UnitCol> scan_unit_uselast_cols(
   for (auto& c : flat)
     TORCH_CHECK(c.present && !c.is_list,
                 "scan_unit_uselast: absent or list column (fallback)");
+  auto da = desc.accessor<int64_t, 2>();
 
-  // pack and merge the per-file keys
+  // merge the per-file keys as decoded; keep-last: source row of each
+  // surviving key, as its index in the concatenation of the files
   std::vector<torch::Tensor> file_keys;
+  std::vector<int64_t> rows;
   for (int64_t f = 0; f < nfiles; f++) {
     auto& pk = flat[(size_t)(f * ncols + pk_ci)].data;
-    file_keys.push_back(pack_key_i64(
-        pk_es == 8 ? pk.view(torch::kInt64) : pk.view(torch::kInt32).to(torch::kInt64)));
+    file_keys.push_back(pk.view(pk_es == 8 ? torch::kInt64 : torch::kInt32));
+    rows.push_back(file_keys.back().numel());
   }
-  auto [keys, order] = merge_key_streams(std::move(file_keys));
+  auto src_idx = unit_merge_src_idx(std::move(file_keys));
+  const int64_t n = src_idx.numel();
 
-  // keep-last: source row of each surviving key
-  int64_t n = keys.numel();
-  auto keep = torch::empty({n}, keys.options().dtype(torch::kUInt8));
-  launch_keep_last((const uint64_t*)keys.data_ptr(), keep.data_ptr<uint8_t>(), n,
-                   cur_stream());
-  auto src_idx = order.index({at::nonzero(keep).view(-1)});
-
-  // concatenate per column, take the survivors (fixed-width data and
-  // validity of every column in fused gathers)
-  auto cols = concat_unit_files(flat, desc, nfiles, ncols);
-  std::vector<torch::Tensor> fixed;
-  for (auto& c : cols) {
-    if (!c.is_string) fixed.push_back(c.data);
-    if (c.validity.defined()) fixed.push_back(c.validity);
+  // take the survivors: fixed-width data and the validity of every column
+  // straight from the per-file buffers in one fused gather; only string
+  // columns are concatenated first
+  auto cols = concat_unit_files(flat, nfiles, ncols);
+  auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(vals.device());
+  std::vector<FileColumn> fcs;
+  for (int64_t c = 0; c < ncols; c++) {
+    auto part = [&](int64_t f) -> const UnitCol& { return flat[(size_t)(f * ncols + c)]; };
+    UnitCol& o = cols[(size_t)c];
+    if (!o.is_string) {
+      int64_t es = da[c][UD_ESIZE];
+      o.data = torch::empty({n * es}, u8);
+      FileColumn fc;
+      fc.es = (int)es;
+      fc.dst = o.data.data_ptr();
+      for (int64_t f = 0; f < nfiles; f++) {
+        TORCH_CHECK(part(f).data.numel() == rows[(size_t)f] * es,
+                    "scan_unit_uselast: a column's row count differs from the pk's");
+        fc.src.push_back(part(f).data.data_ptr());
+      }
+      fcs.push_back(std::move(fc));
+    }
+    bool any_valid = false;
+    for (int64_t f = 0; f < nfiles; f++) any_valid |= part(f).validity.defined();
+    if (any_valid) {
+      // files without a validity count as all ones
+      o.validity = torch::empty({n}, u8);
+      FileColumn fc;
+      fc.es = 1;
+      fc.dst = o.validity.data_ptr();
+      for (int64_t f = 0; f < nfiles; f++) {
+        auto& v = part(f).validity;
+        TORCH_CHECK(!v.defined() || v.numel() == rows[(size_t)f],
+                    "scan_unit_uselast: a validity's row count differs from the pk's");
+        fc.src.push_back(v.defined() ? v.data_ptr() : nullptr);
+      }
+      fcs.push_back(std::move(fc));
+    }
   }
-  auto taken = gather_fixed(std::move(fixed), src_idx);
-  size_t t = 0;
-  for (auto& c : cols) {
-    if (!c.is_string) c.data = taken[t++].view(-1);
-    if (c.validity.defined()) c.validity = taken[t++];
+  gather_files_launch(fcs, rows, src_idx);
+  for (auto& c : cols)
     if (c.is_string)
       std::tie(c.offsets, c.bytes) = take_strings(c.bytes, c.offsets, src_idx);
-  }
   return cols;
 }
 
@@ -1081,6 +1278,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hash_string_column", &hash_string_column);
   m.def("bucket_ids", &bucket_ids);
   m.def("merge_sorted_keys", &merge_key_streams);
+  m.def("unit_merge_src_idx", &unit_merge_src_idx, py::arg("keys"));
+  m.def("gather_files", &gather_files, py::arg("cols"), py::arg("rows"),
+        py::arg("idx"), py::arg("outs") = py::none());
   m.def("group_start_mask", &group_start_mask);
   m.def("pack_key_i64", &pack_key_i64);
   m.def("pack_key_2xi32", &pack_key_2xi32);

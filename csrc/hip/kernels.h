@@ -31,11 +31,47 @@ template <typename T>
 void launch_scatter_valid(const T* dense, const uint8_t* validity,
                           const int64_t* pos, T* out, int64_t n, hipStream_t s);
 
-// kernels.hip — merge
-void launch_merge_pairs(const uint64_t* kA, const uint64_t* vA, int64_t nA,
-                        const uint64_t* kB, const uint64_t* vB, int64_t nB,
-                        uint64_t* kOut, uint64_t* vOut, hipStream_t s);
-void launch_keep_last(const uint64_t* keys, uint8_t* keep, int64_t n, hipStream_t s);
+// kernels.hip — merge. One launch merges up to MERGE_PAIRS_PER_LAUNCH pairs
+// of sorted (key, row) streams, a 2048-row tile per workgroup (the plan:
+// ../cpp/merge_plan.h). MergeTable is passed BY VALUE into
+// merge_round_kernel: this is its only definition.
+constexpr int MERGE_PAIRS_PER_LAUNCH = 16;
+struct MergePairArg {
+  // a stream with rows == nullptr is an input stream: its keys are in the
+  // launch's key format and the row value of element i is base + i. Any
+  // other stream holds packed u64 keys and stored row values. A is the
+  // older stream: first on equal keys.
+  const void* kA;
+  const int64_t* rA;
+  int64_t nA, baseA;
+  const void* kB;
+  const int64_t* rB;
+  int64_t nB, baseB;
+  uint64_t* kOut;  // nA + nB packed keys; unused by the keep-last round
+  int64_t* rOut;   // nA + nB row values (keep-last round: tile slots)
+  int64_t first_tile;  // tiles of this launch before this pair
+};
+struct MergeTable {
+  MergePairArg p[MERGE_PAIRS_PER_LAUNCH];
+  int npairs;
+  int64_t ntiles;        // tiles of all pairs of this launch
+  int64_t* tile_counts;  // keep-last round only: survivors per tile
+};
+enum MergeKeyFormat { MERGE_KEY_I64 = 0, MERGE_KEY_I32 = 1, MERGE_KEY_PACKED = 2 };
+// key_format: how input streams store keys. int64/int32 keys are made
+// order-preserving unsigned in registers (sign bit flipped, int32 widened).
+void launch_merge_round(const MergeTable& tbl, int key_format, hipStream_t s);
+// The last round of a UseLast merge: table of ONE pair (B may be empty).
+// Writes no keys: of every run of equal keys only the last row survives;
+// tile t's surviving row values go to rOut[t * 2048 ...), their number to
+// tile_counts[t].
+void launch_merge_round_keep_last(const MergeTable& tbl, int key_format,
+                                  hipStream_t s);
+// out[csum[t] - counts[t] + i] = slots[t * 2048 + i] for i < counts[t]
+// (csum: inclusive prefix sum of counts)
+void launch_compact_tiles(const int64_t* slots, const int64_t* counts,
+                          const int64_t* csum, int64_t ntiles, int64_t* out,
+                          hipStream_t s);
 void launch_group_start(const uint64_t* keys, uint8_t* start, int64_t n, hipStream_t s);
 void launch_pack_key_i64(const int64_t* x, uint64_t* out, int64_t n, hipStream_t s);
 void launch_pack_key_2xi32(const int32_t* hi, const int32_t* lo, uint64_t* out,
@@ -51,6 +87,22 @@ struct GatherTable {
 };
 void launch_gather_fixed_multi(const GatherTable& tbl, const int64_t* idx,
                                int64_t n, hipStream_t s);
+// gather from per-file buffers: idx[i] is a row of the concatenation of the
+// files in file order; file f holds rows [start[f], start[f + 1]). Rows
+// outside [start[0], start[nfiles]) are left to another launch. A null
+// source pointer stands for a file of ones (a file without validity).
+// Passed BY VALUE into gather_files_kernel: this is its only definition.
+constexpr int GATHER_FILES_MAX_COLS = 16;
+constexpr int GATHER_FILES_MAX_FILES = 16;
+struct GatherFilesTable {
+  const void* src[GATHER_FILES_MAX_COLS][GATHER_FILES_MAX_FILES];
+  void* dst[GATHER_FILES_MAX_COLS];
+  int esize[GATHER_FILES_MAX_COLS];
+  int64_t start[GATHER_FILES_MAX_FILES + 1];
+  int ncols, nfiles;
+};
+void launch_gather_files(const GatherFilesTable& tbl, const int64_t* idx,
+                         int64_t n, hipStream_t s);
 void launch_gather_strings(const uint8_t* src_bytes, const int64_t* src_off,
                            const int64_t* idx, const int64_t* dst_off,
                            uint8_t* dst_bytes, int64_t n, hipStream_t s);

@@ -13,14 +13,15 @@
 // Design notes (per /opt/skills/guides/cdna_hip_programming.md):
 //  - memory-bound kernels: grid-stride, <=2048 workgroups, vectorized
 //    where layout permits (G11/G13);
-//  - merge-path kernel stages key tiles in LDS (G3), 2048-element tiles,
-//    256 threads x 8 elements/thread;
+//  - merge-path kernel stages key and row tiles in LDS (G3), 2048-element
+//    tiles, 256 threads x 8 elements/thread, one launch per merge round;
 //  - all block sizes are multiples of 64 (wave64).
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "../cpp/merge_plan.h"
 #include "../cpp/murmur3.h"
 #include "kernels.h"
 
@@ -161,102 +162,219 @@ __global__ void scatter_valid_kernel(const T* __restrict__ dense,
 }
 
 // ===================================================================== //
-// merge-path pairwise sorted merge (keys u64 + source index u64)
+// batched merge-path rounds (keys u64 + row index i64)
 // ===================================================================== //
-// A is the OLDER stream: on equal keys A's elements are emitted first so
-// the newest row survives dedup-keep-last (UseLast semantics,
-// reference sorted_stream_merger.rs / combiner.rs).
+// One launch merges every pair of a round (MergeTable, kernels.h; the
+// plan: ../cpp/merge_plan.h). A is the OLDER stream of a pair: on equal
+// keys A's elements are emitted first so the newest row survives
+// dedup-keep-last (UseLast semantics, reference sorted_stream_merger.rs /
+// combiner.rs).
 
-__device__ inline int64_t merge_path_search(const uint64_t* A, int64_t nA,
-                                            const uint64_t* B, int64_t nB,
-                                            int64_t d) {
+#define MERGE_VT 8
+#define MERGE_TILE (LS_THREADS * MERGE_VT)  // 2048
+static_assert(MERGE_TILE == MERGE_TILE_ROWS, "tile size of the host plan");
+
+// key i of a stream as an order-preserving u64. Input streams (raw) hold
+// keys in the launch's format KF, every other stream packed keys.
+template <int KF>
+__device__ inline uint64_t merge_load_key(const void* k, bool raw, int64_t i) {
+  if constexpr (KF == MERGE_KEY_I64) {
+    if (raw) return (uint64_t)((const int64_t*)k)[i] ^ 0x8000000000000000ull;
+  } else if constexpr (KF == MERGE_KEY_I32) {
+    if (raw) return (uint64_t)((uint32_t)((const int32_t*)k)[i] ^ 0x80000000u);
+  }
+  return ((const uint64_t*)k)[i];
+}
+
+// merge-path split of diagonal d: how many of the first d merged elements
+// come from A. The whole wave searches: each pass probes 64 split points,
+// so ~4 dependent loads find a split among 2^24 where a binary search
+// needs 24. Every lane of the wave must call it with the same arguments;
+// all lanes return the split.
+template <int KF>
+__device__ inline int64_t merge_path_search_wave(const void* A, bool rawA, int64_t nA,
+                                                 const void* B, bool rawB, int64_t nB,
+                                                 int64_t d, int lane) {
   int64_t lo = d > nB ? d - nB : 0;
   int64_t hi = d < nA ? d : nA;
+  // invariant: pred(mid) = A[mid] <= B[d-mid-1] holds below the split and
+  // fails from it on; lo <= split <= hi
   while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (A[mid] <= B[d - mid - 1]) lo = mid + 1;
-    else hi = mid;
+    int64_t span = hi - lo;
+    int64_t mid = lo + ((span * lane) >> 6);  // in [lo, hi), lane 0 at lo
+    bool pred = merge_load_key<KF>(A, rawA, mid) <= merge_load_key<KF>(B, rawB, d - mid - 1);
+    int c = __popcll(__ballot(pred));  // lanes 0..c-1 hold, lane c fails
+    int64_t nlo = c > 0 ? lo + ((span * (c - 1)) >> 6) + 1 : lo;
+    int64_t nhi = c < 64 ? lo + ((span * c) >> 6) : hi;
+    lo = nlo;
+    hi = nhi;
   }
   return lo;
 }
 
-#define MERGE_VT 8
-#define MERGE_TILE (LS_THREADS * MERGE_VT)  // 2048
+// KEEP_LAST = false: a merge round, keys and rows out.
+// KEEP_LAST = true: the last round of a UseLast merge (one pair): no keys
+// out; a row survives when its successor in merged order has another key.
+template <int KF, bool KEEP_LAST>
+__global__ __launch_bounds__(LS_THREADS) void merge_round_kernel(MergeTable tbl) {
+  // A window then B window (KEEP_LAST: each one element longer where the
+  // stream goes on, for the successor of the tile's last row); after the
+  // merge the same arrays stage the tile's output. +4: the heads read one
+  // past a window's end before the bounds are checked.
+  __shared__ uint64_t sk[MERGE_TILE + 4];
+  __shared__ int64_t sv[MERGE_TILE + 4];
+  __shared__ int64_t s_bounds[2];
+  __shared__ int s_wave_kept[LS_THREADS / 64];
 
-__global__ __launch_bounds__(LS_THREADS) void merge_pairs_kernel(
-    const uint64_t* __restrict__ kA, const uint64_t* __restrict__ vA, int64_t nA,
-    const uint64_t* __restrict__ kB, const uint64_t* __restrict__ vB, int64_t nB,
-    uint64_t* __restrict__ kOut, uint64_t* __restrict__ vOut) {
-  __shared__ uint64_t sk[MERGE_TILE + 2];   // A window then B window
-  __shared__ int64_t s_bounds[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t tile = blockIdx.x; tile < tbl.ntiles; tile += gridDim.x) {
+    int j = 0;
+    while (j + 1 < tbl.npairs && tbl.p[j + 1].first_tile <= tile) j++;
+    const void* kA = tbl.p[j].kA;
+    const void* kB = tbl.p[j].kB;
+    const int64_t* rA = tbl.p[j].rA;
+    const int64_t* rB = tbl.p[j].rB;
+    const int64_t nA = tbl.p[j].nA, nB = tbl.p[j].nB;
+    const bool rawA = rA == nullptr, rawB = rB == nullptr;
+    const int64_t total = nA + nB;
+    const int64_t d0 = (tile - tbl.p[j].first_tile) * MERGE_TILE;
+    const int64_t d1 = d0 + MERGE_TILE < total ? d0 + MERGE_TILE : total;
 
-  int64_t total = nA + nB;
-  for (int64_t tile = blockIdx.x;; tile += gridDim.x) {
-    int64_t d0 = tile * MERGE_TILE;
-    if (d0 >= total) break;
-    int64_t d1 = d0 + MERGE_TILE;
-    if (d1 > total) d1 = total;
-
-    if (threadIdx.x == 0) {
-      s_bounds[0] = merge_path_search(kA, nA, kB, nB, d0);
-      s_bounds[1] = merge_path_search(kA, nA, kB, nB, d1);
+    // waves 0 and 1 find the tile's two splits side by side
+    if (wave < 2) {
+      int64_t a = merge_path_search_wave<KF>(kA, rawA, nA, kB, rawB, nB,
+                                             wave ? d1 : d0, lane);
+      if (lane == 0) s_bounds[wave] = a;
     }
     __syncthreads();
-    int64_t a0 = s_bounds[0], a1 = s_bounds[1];
-    int64_t b0 = d0 - a0, b1 = d1 - a1;
-    int aCount = (int)(a1 - a0);
-    int bCount = (int)(b1 - b0);
+    const int64_t a0 = s_bounds[0], a1 = s_bounds[1];
+    const int64_t b0 = d0 - a0, b1 = d1 - a1;
+    const int aCount = (int)(a1 - a0), bCount = (int)(b1 - b0);
+    const int aExt = aCount + ((KEEP_LAST && a1 < nA) ? 1 : 0);
+    const int bExt = bCount + ((KEEP_LAST && b1 < nB) ? 1 : 0);
 
-    // stage key windows in LDS: [0,aCount) = A, [aCount, aCount+bCount) = B
-    for (int i = threadIdx.x; i < aCount; i += blockDim.x) sk[i] = kA[a0 + i];
-    for (int i = threadIdx.x; i < bCount; i += blockDim.x)
-      sk[aCount + i] = kB[b0 + i];
+    // stage keys and rows: [0, aExt) = A, [aExt, aExt + bExt) = B
+    for (int i = threadIdx.x; i < aExt; i += LS_THREADS) {
+      sk[i] = merge_load_key<KF>(kA, rawA, a0 + i);
+      sv[i] = rawA ? tbl.p[j].baseA + a0 + i : rA[a0 + i];
+    }
+    for (int i = threadIdx.x; i < bExt; i += LS_THREADS) {
+      sk[aExt + i] = merge_load_key<KF>(kB, rawB, b0 + i);
+      sv[aExt + i] = rawB ? tbl.p[j].baseB + b0 + i : rB[b0 + i];
+    }
     __syncthreads();
 
     // each thread merges MERGE_VT outputs starting at its local diagonal
-    int local_d = threadIdx.x * MERGE_VT;
-    int out_n = (int)(d1 - d0);
-    if (local_d < out_n) {
-      // local merge-path within LDS
+    const int out_n = (int)(d1 - d0);
+    const int local_d = threadIdx.x * MERGE_VT;
+    int count = out_n - local_d;
+    count = count < 0 ? 0 : count > MERGE_VT ? MERGE_VT : count;
+    uint64_t ok[MERGE_VT];
+    int64_t ov[MERGE_VT];
+    int ai = 0, bi = 0;
+    if (count) {
       int lo = local_d > bCount ? local_d - bCount : 0;
       int hi = local_d < aCount ? local_d : aCount;
       while (lo < hi) {
         int mid = (lo + hi) >> 1;
-        if (sk[mid] <= sk[aCount + local_d - mid - 1]) lo = mid + 1;
+        if (sk[mid] <= sk[aExt + local_d - mid - 1]) lo = mid + 1;
         else hi = mid;
       }
-      int ai = lo;
-      int bi = local_d - lo;
-      int64_t base = d0 + local_d;
-      int count = out_n - local_d < MERGE_VT ? out_n - local_d : MERGE_VT;
+      ai = lo;
+      bi = local_d - lo;
+    }
+    uint64_t ka = sk[ai], kb = sk[aExt + bi];
+    int64_t va = sv[ai], vb = sv[aExt + bi];
 #pragma unroll
-      for (int k = 0; k < MERGE_VT; k++) {
-        if (k >= count) break;
-        bool takeA;
-        if (ai >= aCount) takeA = false;
-        else if (bi >= bCount) takeA = true;
-        else takeA = sk[ai] <= sk[aCount + bi];
+    for (int k = 0; k < MERGE_VT; k++) {
+      if (k < count) {
+        bool takeA = bi >= bCount || (ai < aCount && ka <= kb);
         if (takeA) {
-          kOut[base + k] = sk[ai];
-          vOut[base + k] = vA[a0 + ai];
+          ok[k] = ka;
+          ov[k] = va;
           ai++;
+          ka = sk[ai];
+          va = sv[ai];
         } else {
-          kOut[base + k] = sk[aCount + bi];
-          vOut[base + k] = vB[b0 + bi];
+          ok[k] = kb;
+          ov[k] = vb;
           bi++;
+          kb = sk[aExt + bi];
+          vb = sv[aExt + bi];
         }
       }
     }
-    __syncthreads();
+
+    if constexpr (!KEEP_LAST) {
+      __syncthreads();  // every thread is done with the windows
+#pragma unroll
+      for (int k = 0; k < MERGE_VT; k++) {
+        if (k < count) {
+          sk[local_d + k] = ok[k];
+          sv[local_d + k] = ov[k];
+        }
+      }
+      __syncthreads();
+      uint64_t* kOut = tbl.p[j].kOut + d0;
+      int64_t* rOut = tbl.p[j].rOut + d0;
+      for (int i = threadIdx.x; i < out_n; i += LS_THREADS) {
+        kOut[i] = sk[i];
+        rOut[i] = sv[i];
+      }
+    } else {
+      // the successor of this thread's last row is the smaller head left
+      // (ka, kb): inside the tile, or the element after the window. No
+      // head left: the last row of all, which is kept.
+      const bool hasA = ai < aExt, hasB = bi < bExt;
+      const uint64_t succ = hasA && hasB ? (ka <= kb ? ka : kb) : hasA ? ka : kb;
+      const bool has_succ = hasA || hasB;
+      unsigned keep = 0;
+#pragma unroll
+      for (int k = 0; k < MERGE_VT; k++) {
+        if (k < count) {
+          bool kp = k + 1 < count ? ok[k] != ok[k + 1] : (!has_succ || ok[k] != succ);
+          keep |= (unsigned)kp << k;
+        }
+      }
+      // exclusive scan of the kept counts over the workgroup
+      const int mine = __popc(keep);
+      int incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      if (lane == 63) s_wave_kept[wave] = incl;
+      __syncthreads();  // also: every thread is done with the windows
+      int pos = incl - mine, tile_kept = 0;
+#pragma unroll
+      for (int w = 0; w < LS_THREADS / 64; w++) {
+        if (w < wave) pos += s_wave_kept[w];
+        tile_kept += s_wave_kept[w];
+      }
+#pragma unroll
+      for (int k = 0; k < MERGE_VT; k++) {
+        if (keep >> k & 1) sv[pos++] = ov[k];
+      }
+      __syncthreads();
+      int64_t* slot = tbl.p[j].rOut + d0;
+      for (int i = threadIdx.x; i < tile_kept; i += LS_THREADS) slot[i] = sv[i];
+      if (threadIdx.x == 0) tbl.tile_counts[tile] = tile_kept;
+    }
+    __syncthreads();  // the next tile reuses the arrays
   }
 }
 
-// keep-last mask over sorted keys: keep[i] = (i == n-1) || key[i] != key[i+1]
-__global__ void keep_last_mask_kernel(const uint64_t* __restrict__ keys,
-                                      uint8_t* __restrict__ keep, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    keep[i] = (i == n - 1) || (keys[i] != keys[i + 1]);
+// moves the survivors of every tile of the keep-last round to their place
+__global__ void compact_tiles_kernel(const int64_t* __restrict__ slots,
+                                     const int64_t* __restrict__ counts,
+                                     const int64_t* __restrict__ csum,
+                                     int64_t ntiles, int64_t* __restrict__ out) {
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t cnt = counts[tile];
+    const int64_t* src = slots + tile * MERGE_TILE;
+    int64_t* dst = out + (csum[tile] - cnt);
+    for (int64_t i = threadIdx.x; i < cnt; i += blockDim.x) dst[i] = src[i];
   }
 }
 
@@ -309,6 +427,40 @@ __global__ void gather_fixed_multi_kernel(GatherTable tbl,
         case 2: ((uint16_t*)tbl.dst[c])[i] = ((const uint16_t*)tbl.src[c])[s]; break;
         case 4: ((uint32_t*)tbl.dst[c])[i] = ((const uint32_t*)tbl.src[c])[s]; break;
         default: ((uint64_t*)tbl.dst[c])[i] = ((const uint64_t*)tbl.src[c])[s]; break;
+      }
+    }
+  }
+}
+
+// the same gather straight from the per-file buffers of a scan unit
+// (struct GatherFilesTable, kernels.h): no concatenated copy of the
+// columns is made first. The file of a row is found by counting the row
+// starts at or below it (an upper bound over <= 16 entries held in LDS).
+__global__ __launch_bounds__(LS_THREADS) void gather_files_kernel(
+    GatherFilesTable tbl, const int64_t* __restrict__ idx, int64_t n) {
+  __shared__ const void* s_src[GATHER_FILES_MAX_COLS * GATHER_FILES_MAX_FILES];
+  __shared__ int64_t s_start[GATHER_FILES_MAX_FILES + 1];
+  for (int i = threadIdx.x; i < GATHER_FILES_MAX_COLS * GATHER_FILES_MAX_FILES;
+       i += LS_THREADS)
+    s_src[i] = tbl.src[i / GATHER_FILES_MAX_FILES][i % GATHER_FILES_MAX_FILES];
+  if (threadIdx.x <= GATHER_FILES_MAX_FILES) s_start[threadIdx.x] = tbl.start[threadIdx.x];
+  __syncthreads();
+  const int nfiles = tbl.nfiles;
+  const int64_t lo = tbl.start[0], hi = tbl.start[nfiles];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t s = idx[i];
+    if (s < lo || s >= hi) continue;
+    int f = 0;
+    for (int j = 1; j < nfiles; j++) f += s_start[j] <= s;
+    int64_t r = s - s_start[f];
+    for (int c = 0; c < tbl.ncols; c++) {
+      const void* p = s_src[c * GATHER_FILES_MAX_FILES + f];
+      switch (tbl.esize[c]) {
+        case 1: ((uint8_t*)tbl.dst[c])[i] = p ? ((const uint8_t*)p)[r] : (uint8_t)1; break;
+        case 2: ((uint16_t*)tbl.dst[c])[i] = p ? ((const uint16_t*)p)[r] : (uint16_t)1; break;
+        case 4: ((uint32_t*)tbl.dst[c])[i] = p ? ((const uint32_t*)p)[r] : 1u; break;
+        default: ((uint64_t*)tbl.dst[c])[i] = p ? ((const uint64_t*)p)[r] : 1ull; break;
       }
     }
   }
@@ -466,18 +618,33 @@ template void launch_scatter_valid<uint16_t>(const uint16_t*, const uint8_t*, co
 template void launch_scatter_valid<uint32_t>(const uint32_t*, const uint8_t*, const int64_t*, uint32_t*, int64_t, hipStream_t);
 template void launch_scatter_valid<uint64_t>(const uint64_t*, const uint8_t*, const int64_t*, uint64_t*, int64_t, hipStream_t);
 
-void launch_merge_pairs(const uint64_t* kA, const uint64_t* vA, int64_t nA,
-                        const uint64_t* kB, const uint64_t* vB, int64_t nB,
-                        uint64_t* kOut, uint64_t* vOut, hipStream_t s) {
-  int64_t ntiles = (nA + nB + MERGE_TILE - 1) / MERGE_TILE;
-  int blocks = ntiles > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : (int)ntiles;
-  hipLaunchKernelGGL(merge_pairs_kernel, dim3(blocks), dim3(LS_THREADS), 0, s,
-                     kA, vA, nA, kB, vB, nB, kOut, vOut);
+template <bool KEEP_LAST>
+static void launch_merge_round_t(const MergeTable& tbl, int key_format, hipStream_t s) {
+  if (tbl.ntiles <= 0) return;  // a grid of 0 blocks is an error
+  dim3 g(tbl.ntiles > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : (int)tbl.ntiles), b(LS_THREADS);
+  switch (key_format) {
+    case MERGE_KEY_I64: hipLaunchKernelGGL((merge_round_kernel<MERGE_KEY_I64, KEEP_LAST>), g, b, 0, s, tbl); break;
+    case MERGE_KEY_I32: hipLaunchKernelGGL((merge_round_kernel<MERGE_KEY_I32, KEEP_LAST>), g, b, 0, s, tbl); break;
+    default: hipLaunchKernelGGL((merge_round_kernel<MERGE_KEY_PACKED, KEEP_LAST>), g, b, 0, s, tbl); break;
+  }
 }
 
-void launch_keep_last(const uint64_t* keys, uint8_t* keep, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(keep_last_mask_kernel, dim3(ls_blocks(n)), dim3(LS_THREADS), 0, s,
-                     keys, keep, n);
+void launch_merge_round(const MergeTable& tbl, int key_format, hipStream_t s) {
+  launch_merge_round_t<false>(tbl, key_format, s);
+}
+
+void launch_merge_round_keep_last(const MergeTable& tbl, int key_format,
+                                  hipStream_t s) {
+  launch_merge_round_t<true>(tbl, key_format, s);
+}
+
+void launch_compact_tiles(const int64_t* slots, const int64_t* counts,
+                          const int64_t* csum, int64_t ntiles, int64_t* out,
+                          hipStream_t s) {
+  if (ntiles <= 0) return;
+  hipLaunchKernelGGL(compact_tiles_kernel,
+                     dim3(ntiles > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : (int)ntiles),
+                     dim3(LS_THREADS), 0, s, slots, counts, csum, ntiles, out);
 }
 
 void launch_group_start(const uint64_t* keys, uint8_t* start, int64_t n, hipStream_t s) {
@@ -500,6 +667,13 @@ void launch_gather_fixed_multi(const GatherTable& tbl, const int64_t* idx,
                                int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(gather_fixed_multi_kernel, dim3(ls_blocks(n)),
                      dim3(LS_THREADS), 0, s, tbl, idx, n);
+}
+
+void launch_gather_files(const GatherFilesTable& tbl, const int64_t* idx,
+                         int64_t n, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(gather_files_kernel, dim3(ls_blocks(n)), dim3(LS_THREADS),
+                     0, s, tbl, idx, n);
 }
 
 void launch_gather_strings(const uint8_t* src_bytes, const int64_t* src_off,

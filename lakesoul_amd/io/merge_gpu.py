@@ -4,7 +4,7 @@ Mirrors merge_cpu.py semantics exactly (same contract as the reference's
 SortedStreamMerger + merge operators); GPU tests compare the two.
 
 Fast path: integer PKs that pack into a u64 order-preserving key use the
-hand-written merge-path kernel (csrc/hip/kernels.hip merge_pairs_kernel,
+hand-written merge-path kernel (csrc/hip/kernels.hip merge_round_kernel,
 driven by _hip.merge_sorted_keys) to exploit per-file sortedness — K
 files merge in ceil(log2 K) passes.
 Generic path: iterated stable argsort (lexsort) on the concatenated keys.
