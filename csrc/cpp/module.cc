@@ -15,6 +15,7 @@
 #include "murmur3.h"
 #include "parquet_file.h"
 #include "read_unit.h"
+#include "str_pred.h"
 #include "str_seg.h"
 #include "str_walk.h"
 #include "unit_desc.h"
@@ -1141,6 +1142,75 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     if (!ok) return py::make_tuple(py::none(), c->rounds);
     return py::make_tuple(py::bytes((const char*)out.get(), (size_t)rs), c->rounds);
   }, py::arg("frame"), py::arg("lanes"), py::arg("rs"));
+  // string predicates (str_pred.h): the operand compilers and the host twin
+  // of the GPU kernel. An operand is (bytes uint8, meta int32).
+  m.def("str_pred_compile_literal", [](py::bytes lit) {
+    std::string b = lit;
+    std::vector<uint8_t> bytes;
+    std::vector<int32_t> meta;
+    lspred::compile_literal((const uint8_t*)b.data(), (int64_t)b.size(), bytes, meta);
+    return py::make_tuple(torch::tensor(bytes, torch::kUInt8),
+                          torch::tensor(meta, torch::kInt32));
+  }, py::arg("literal"));
+  m.def("str_pred_compile_set", [](std::vector<py::bytes> lits) {
+    std::vector<std::string> v;
+    for (auto& l : lits) v.push_back((std::string)l);
+    std::vector<uint8_t> bytes;
+    std::vector<int32_t> meta;
+    lspred::compile_set(std::move(v), bytes, meta);
+    return py::make_tuple(torch::tensor(bytes, torch::kUInt8),
+                          torch::tensor(meta, torch::kInt32));
+  }, py::arg("literals"));
+  m.def("str_pred_compile_like", [](py::bytes pattern, int64_t escape, bool utf8) {
+    std::string b = pattern;
+    std::vector<uint8_t> bytes;
+    std::vector<int32_t> meta;
+    lspred::compile_like((const uint8_t*)b.data(), (int64_t)b.size(),
+                         escape < 0 || escape > 255 ? -1 : (int)escape, utf8,
+                         bytes, meta);
+    return py::make_tuple(torch::tensor(bytes, torch::kUInt8),
+                          torch::tensor(meta, torch::kInt32));
+  }, py::arg("pattern"), py::arg("escape"), py::arg("utf8"));
+  m.def("str_pred_mask", [](torch::Tensor offsets, torch::Tensor bytes,
+                            c10::optional<torch::Tensor> validity, int64_t op,
+                            torch::Tensor op_bytes, torch::Tensor op_meta) {
+    TORCH_CHECK(!offsets.is_cuda() && !bytes.is_cuda() && !op_bytes.is_cuda() &&
+                !op_meta.is_cuda(), "str_pred_mask: CPU tensors only");
+    TORCH_CHECK(op >= 0 && op < lspred::OP_COUNT, "str_pred_mask: bad op");
+    TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1, "str_pred_mask: offsets");
+    TORCH_CHECK(bytes.scalar_type() == torch::kUInt8 &&
+                op_bytes.scalar_type() == torch::kUInt8 &&
+                op_meta.scalar_type() == torch::kInt32, "str_pred_mask: dtypes");
+    offsets = offsets.contiguous();
+    bytes = bytes.contiguous();
+    op_bytes = op_bytes.contiguous();
+    op_meta = op_meta.contiguous();
+    TORCH_CHECK(op_meta.numel() >= lspred::min_meta((int)op), "str_pred_mask: short operand");
+    int64_t n = offsets.numel() - 1;
+    torch::Tensor val;
+    const uint8_t* vp = nullptr;
+    if (validity && validity->numel()) {
+      TORCH_CHECK(validity->numel() == n && (validity->scalar_type() == torch::kUInt8 ||
+                                             validity->scalar_type() == torch::kBool),
+                  "str_pred_mask: validity");
+      val = validity->contiguous();
+      vp = (const uint8_t*)val.data_ptr();
+    }
+    auto out = torch::empty({n}, torch::kBool);
+    lspred::Operand o{op_bytes.numel() ? op_bytes.data_ptr<uint8_t>() : nullptr,
+                      op_bytes.numel(), op_meta.data_ptr<int32_t>(), op_meta.numel()};
+    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
+    if (offsets.scalar_type() == torch::kInt32)
+      lspred::str_pred_mask_host(offsets.data_ptr<int32_t>(), n, bp, bytes.numel(),
+                                 vp, (int)op, o, (uint8_t*)out.data_ptr());
+    else if (offsets.scalar_type() == torch::kInt64)
+      lspred::str_pred_mask_host(offsets.data_ptr<int64_t>(), n, bp, bytes.numel(),
+                                 vp, (int)op, o, (uint8_t*)out.data_ptr());
+    else
+      TORCH_CHECK(false, "str_pred_mask: offsets must be int32 or int64");
+    return out;
+  }, py::arg("offsets"), py::arg("bytes"), py::arg("validity"), py::arg("op"),
+     py::arg("op_bytes"), py::arg("op_meta"));
   m.def("hash_columns_cpu", &hash_columns_cpu);
   m.def("hash_string_column_cpu", &hash_string_column_cpu);
   m.def("bucket_ids_from_hashes", &bucket_ids_from_hashes);

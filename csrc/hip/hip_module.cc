@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../cpp/merge_plan.h"
+#include "../cpp/str_pred.h"
 #include "../cpp/unit_desc.h"
 #include "kernels.h"
 
@@ -456,6 +457,81 @@ static torch::Tensor bytes_ne_mask(torch::Tensor offsets, torch::Tensor bytes,
                        pattern.data_ptr<uint8_t>(), (int)pattern.numel(),
                        out.data_ptr<uint8_t>(), n, cur_stream());
   return out;
+}
+
+// ---- string predicates ------------------------------------------------ //
+
+// One leaf predicate over a string column (str_pred.hip). The operand is
+// what lakesoul_amd._cpp.str_pred_compile_* made, moved to the device.
+// shape: "rows", "wave" or None (picked from the mean value length, which
+// the tensor sizes give without a sync). No host sync, no status read-back.
+// The thresholds are the measured crossovers of profiles/r07_gpu_str_pred.md:
+// a compare that runs to a value's last byte is faster a wave per row from
+// 1 KB values on, a LIKE that searches for a middle segment from 96 bytes on.
+constexpr int64_t STR_PRED_WAVE_MEAN_LEN_CMP = 1024;
+constexpr int64_t STR_PRED_WAVE_MEAN_LEN_LIKE = 96;
+
+static bool str_pred_pick_wave(int64_t op, int64_t nrows, int64_t nbytes) {
+  int64_t at = op >= lspred::OP_LIKE ? STR_PRED_WAVE_MEAN_LEN_LIKE
+                                     : STR_PRED_WAVE_MEAN_LEN_CMP;
+  return nrows > 0 && nbytes / nrows >= at;
+}
+
+static torch::Tensor str_pred_mask(torch::Tensor offsets, torch::Tensor bytes,
+                                   c10::optional<torch::Tensor> validity,
+                                   int64_t op, torch::Tensor op_bytes,
+                                   torch::Tensor op_meta,
+                                   c10::optional<std::string> shape,
+                                   c10::optional<torch::Tensor> out) {
+  CHECK_GPU(offsets);
+  CHECK_GPU_NONEMPTY(bytes);
+  CHECK_GPU_NONEMPTY(op_bytes);
+  CHECK_GPU(op_meta);
+  TORCH_CHECK(op >= 0 && op < lspred::OP_COUNT, "str_pred_mask: bad op");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1, "str_pred_mask: offsets");
+  TORCH_CHECK(bytes.scalar_type() == torch::kUInt8 &&
+              op_bytes.scalar_type() == torch::kUInt8 &&
+              op_meta.scalar_type() == torch::kInt32, "str_pred_mask: dtypes");
+  TORCH_CHECK(op_meta.numel() >= lspred::min_meta((int)op),
+              "str_pred_mask: short operand");
+  int64_t n = offsets.numel() - 1;
+  const uint8_t* vp = nullptr;
+  if (validity && validity->numel()) {
+    CHECK_GPU(*validity);
+    TORCH_CHECK(validity->numel() == n &&
+                (validity->scalar_type() == torch::kUInt8 ||
+                 validity->scalar_type() == torch::kBool), "str_pred_mask: validity");
+    vp = (const uint8_t*)validity->data_ptr();
+  }
+  torch::Tensor o;
+  if (out) {
+    o = *out;
+    CHECK_GPU(o);
+    TORCH_CHECK(o.scalar_type() == torch::kBool && o.numel() == n,
+                "str_pred_mask: out must be n bools");
+  } else {
+    o = torch::empty({n}, offsets.options().dtype(torch::kBool));
+  }
+  int wave;
+  if (shape) {
+    TORCH_CHECK(*shape == "rows" || *shape == "wave", "str_pred_mask: shape");
+    wave = *shape == "wave";
+  } else {
+    wave = str_pred_pick_wave(op, n, bytes.numel());
+  }
+  const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
+  const uint8_t* obp = op_bytes.numel() ? op_bytes.data_ptr<uint8_t>() : nullptr;
+  if (offsets.scalar_type() == torch::kInt32)
+    launch_str_pred(offsets.data_ptr<int32_t>(), bp, bytes.numel(), vp, (int)op,
+                    obp, op_bytes.numel(), op_meta.data_ptr<int32_t>(),
+                    op_meta.numel(), wave, (uint8_t*)o.data_ptr(), n, cur_stream());
+  else if (offsets.scalar_type() == torch::kInt64)
+    launch_str_pred(offsets.data_ptr<int64_t>(), bp, bytes.numel(), vp, (int)op,
+                    obp, op_bytes.numel(), op_meta.data_ptr<int32_t>(),
+                    op_meta.numel(), wave, (uint8_t*)o.data_ptr(), n, cur_stream());
+  else
+    TORCH_CHECK(false, "str_pred_mask: offsets must be int32 or int64");
+  return o;
 }
 
 // ---- segmented merge ops ---------------------------------------------- //
@@ -1288,6 +1364,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("take_strings", &take_strings);
   m.def("gather_strings", &gather_strings);
   m.def("bytes_ne_mask", &bytes_ne_mask);
+  m.def("str_pred_mask", &str_pred_mask, py::arg("offsets"), py::arg("bytes"),
+        py::arg("validity"), py::arg("op"), py::arg("op_bytes"),
+        py::arg("op_meta"), py::arg("shape") = py::none(),
+        py::arg("out") = py::none());
+  m.def("str_pred_lds_budget", []() { return str_pred_lds_budget(); });
+  m.def("str_pred_pick_shape", [](int64_t op, int64_t nrows, int64_t nbytes) {
+    return std::string(str_pred_pick_wave(op, nrows, nbytes) ? "wave" : "rows");
+  }, py::arg("op"), py::arg("nrows"), py::arg("nbytes"),
+        "the shape str_pred_mask takes when none is forced");
   m.def("segmented_sum", &segmented_sum);
   m.def("segmented_last", &segmented_last);
 }

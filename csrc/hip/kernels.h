@@ -184,6 +184,21 @@ void launch_dict_str_copy(const uint8_t* dict_bytes, int64_t dict_len,
                           int64_t nrows, uint8_t* dst, int64_t total,
                           hipStream_t s);
 
+// str_pred.hip — one leaf string predicate (../cpp/str_pred.h: ops and the
+// compiled operand op_bytes / op_meta) over an offsets + bytes column;
+// OffT is int32_t or int64_t and offsets[0] need not be 0; out[i] =
+// validity[i] && pred(row i). wave_shape: a wave per row instead of a
+// thread per row. An operand of at most STR_PRED_LDS_BUDGET bytes is staged
+// in LDS.
+constexpr int64_t STR_PRED_LDS_BUDGET = 16384;
+int64_t str_pred_lds_budget();
+template <typename OffT>
+void launch_str_pred(const OffT* offsets, const uint8_t* bytes, int64_t nbytes,
+                     const uint8_t* validity, int op, const uint8_t* op_bytes,
+                     int64_t op_nbytes, const int32_t* op_meta,
+                     int64_t op_nmeta, int wave_shape, uint8_t* out, int64_t n,
+                     hipStream_t s);
+
 // snappy.hip, lz4.hip, zstd.hip, zstd_huf.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,

@@ -24,7 +24,7 @@ from __future__ import annotations
 import struct
 from typing import Dict, List, Optional, Tuple
 
-from .filters import And, Cmp, Expr, IsNull, Literal, Not, Or
+from .filters import And, Cmp, Expr, IsNull, Like, Literal, Not, Or, pattern_expr
 from .schema import Schema
 
 
@@ -122,6 +122,7 @@ _CMP_FUNCS = {
     "lt": "lt",
     "lte": "lteq",
 }
+_PATTERN_FUNCS = ("like", "starts_with", "ends_with", "contains")
 _CMP_SWAP = {"eq": "eq", "noteq": "noteq", "gt": "lt", "gteq": "lteq",
              "lt": "gt", "lteq": "gteq"}
 
@@ -328,6 +329,23 @@ def _scalar_function(fn_msg: bytes, ctx: _Ctx) -> Expr:
                 return IsNull(col, negate=True)
             return Literal(True)
         return Cmp(col, op, _coerce(val, col, ctx))
+    if name in _PATTERN_FUNCS:
+        # (column, string literal[, escape character literal for like])
+        if len(args) not in ((2, 3) if name == "like" else (2,)):
+            raise SubstraitError(f"{name} needs a column and a literal")
+        (ka, col), (kb, val) = _value_operand(args[0], ctx), _value_operand(args[1], ctx)
+        if ka != "col" or kb != "lit" or not isinstance(val, (str, bytes)):
+            raise SubstraitError(f"{name} must match a column against a string literal")
+        val = _coerce(val, col, ctx)
+        if name != "like":
+            return pattern_expr(col, name, val)
+        escape = "\\"
+        if len(args) == 3:
+            ke, ev = _value_operand(args[2], ctx)
+            if ke != "lit" or not isinstance(ev, (str, bytes)) or len(ev) > 1:
+                raise SubstraitError("like escape must be a one-character literal")
+            escape = ev.decode() if isinstance(ev, bytes) else ev
+        return Like(col, val, escape=escape)
     raise SubstraitError(f"unsupported function {name}")
 
 
@@ -541,6 +559,13 @@ def _enc_pred(e: Expr, schema: Schema, ft: _FnTable) -> bytes:
             return _w_len(8, body)         # Expression.singular_or_list
         return _enc_fn(ft.anchor(_INV_CMP[e.op]),
                        [_enc_expr_col(idx), _enc_expr_lit(e.value)])
+    if isinstance(e, Like):
+        if e.negate:
+            # not(like) would let NULL rows through
+            raise SubstraitError("cannot encode NOT LIKE")
+        return _enc_fn(ft.anchor("like"),
+                       [_enc_expr_col(names.index(e.col)), _enc_expr_lit(e.pattern),
+                        _enc_expr_lit(e.escape)])
     raise SubstraitError(f"cannot encode {type(e).__name__}")
 
 

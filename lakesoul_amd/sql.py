@@ -18,7 +18,7 @@ import re
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .io.filters import And, Cmp, Expr, IsNull, Literal, Not, Or
+from .io.filters import And, Cmp, Expr, IsNull, Like, Literal, Not, Or
 
 _TOKEN_RE = re.compile(
     r"""\s*(?:
@@ -38,7 +38,7 @@ _KEYWORDS = {
     "update", "set", "delete", "offset", "having", "timestamp", "explain",
     "create", "table", "drop", "primary", "key", "hash", "buckets",
     "partition", "if", "exists", "alter", "add", "column", "compact",
-    "vacuum", "keep",
+    "vacuum", "keep", "like", "escape",
 }
 
 _AGGS = {"count", "sum", "min", "max", "avg"}
@@ -633,6 +633,17 @@ class _Parser:
             for x in vals[1:]:
                 e = Or(e, Cmp(col, "eq", x))
             return Not(e) if neg else e
+        if (k, v) == ("kw", "like") or ((k, v) == ("kw", "not") and self.peek(1) == ("kw", "like")):
+            neg = self.accept("kw", "not")
+            self.expect("kw", "like")
+            pat = self.expect("str")
+            escape = "\\"
+            if self.accept("kw", "escape"):
+                escape = self.expect("str")
+                if len(escape.encode()) > 1:
+                    raise SqlError("ESCAPE takes one character")
+            # NOT LIKE keeps NULL rows out, which Not(...) would not
+            return Like(col, pat, negate=neg, escape=escape)
         if (k, v) == ("kw", "between") or ((k, v) == ("kw", "not") and self.peek(1) == ("kw", "between")):
             neg = self.accept("kw", "not")
             self.expect("kw", "between")
@@ -877,6 +888,9 @@ def _pd_eval(expr: Expr, df, col):
         if op == "lteq":
             return series <= v
         raise SqlError(f"unsupported join filter op {op}")
+    if isinstance(expr, Like):
+        return df[col(expr.col)].map(
+            lambda x: False if pd.isna(x) else expr._match_one(x)).astype(bool)
     raise SqlError(f"unsupported filter node {type(expr).__name__} in join")
 
 
@@ -1382,7 +1396,7 @@ def _strip_quals(q: Query, valid_quals, passthrough=()) -> None:
             walk(e.right)
         elif isinstance(e, Not):
             walk(e.inner)
-        elif isinstance(e, (Cmp, IsNull)):
+        elif isinstance(e, (Cmp, IsNull, Like)):
             e.col = strip(e.col)
 
     walk(q.where)

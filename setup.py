@@ -50,6 +50,7 @@ if _WITH_HIP:
                 os.path.join("csrc", "hip", "zstd_huf.hip"),
                 os.path.join("csrc", "hip", "delta.hip"),
                 os.path.join("csrc", "hip", "strings.hip"),
+                os.path.join("csrc", "hip", "str_pred.hip"),
             ],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
