@@ -2,7 +2,10 @@
 // the image has the runtime lib but no dev header), snappy decode and the
 // LZ4 block codec implemented from the format specs (the reference's
 // default codec is zstd(1), writer/mod.rs:224-245; snappy read support is
-// for foreign files; LZ4_RAW is read and written, lz4_dec.h).
+// for foreign files; LZ4_RAW is read and written, lz4_dec.h). GZIP pages
+// (codec 2: gzip members or a zlib stream) are read by the DEFLATE decoder
+// of inflate.h, written from RFC 1950-1952 with no zlib; GZIP is not
+// written.
 #pragma once
 
 #include <cstddef>
@@ -12,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "inflate.h"
 #include "lz4_dec.h"
 
 extern "C" {
@@ -117,6 +121,15 @@ inline void lz4_hadoop_decompress_into(uint8_t* dst, size_t dst_n,
     throw std::runtime_error("lz4 (hadoop) decompress failed");
 }
 
+// -- GZIP (inflate.h): gzip members (CRC32 and ISIZE verified) or a zlib
+// stream (Adler-32 verified); read only.
+
+inline void gzip_decompress_into(uint8_t* dst, size_t dst_n, const uint8_t* src,
+                                 size_t src_n) {
+  if (!lsinfl::inflate_page(dst, (int64_t)dst_n, src, (int64_t)src_n))
+    throw std::runtime_error("gzip decompress failed");
+}
+
 inline void decompress_into(int codec, uint8_t* dst, size_t dst_n,
                             const uint8_t* src, size_t src_n) {
   switch (codec) {
@@ -126,6 +139,9 @@ inline void decompress_into(int codec, uint8_t* dst, size_t dst_n,
       return;
     case 1:  // SNAPPY
       snappy_decompress_into(dst, dst_n, src, src_n);
+      return;
+    case 2:  // GZIP
+      gzip_decompress_into(dst, dst_n, src, src_n);
       return;
     case 5:  // LZ4 (Hadoop framing, or a raw block from old writers)
       lz4_hadoop_decompress_into(dst, dst_n, src, src_n);

@@ -593,14 +593,14 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
                                  int64_t nthreads, bool pin, bool gpu_snappy,
                                  bool gpu_zstd, double gpu_zstd_frac,
                                  bool gpu_delta, bool gpu_huf, bool gpu_lz4,
-                                 bool gpu_strings) {
+                                 bool gpu_strings, bool gpu_gzip) {
   (void)nthreads;
   std::unique_ptr<UnitStage> st;
   auto t0 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
     st = read_unit_stage1(paths, names, gpu_snappy, gpu_zstd, gpu_zstd_frac,
-                          gpu_delta, gpu_huf, gpu_lz4, gpu_strings);
+                          gpu_delta, gpu_huf, gpu_lz4, gpu_strings, gpu_gzip);
   }
   auto t1 = std::chrono::steady_clock::now();
   UnitStage& ud = *st;
@@ -637,6 +637,9 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   torch::Tensor ljobs = torch::empty({(int64_t)ud.lz4_jobs.size()}, torch::kInt64);
   if (!ud.lz4_jobs.empty())
     std::memcpy(ljobs.data_ptr(), ud.lz4_jobs.data(), ud.lz4_jobs.size() * 8);
+  torch::Tensor gjobs = torch::empty({(int64_t)ud.gzip_jobs.size()}, torch::kInt64);
+  if (!ud.gzip_jobs.empty())
+    std::memcpy(gjobs.data_ptr(), ud.gzip_jobs.data(), ud.gzip_jobs.size() * 8);
   auto t2 = std::chrono::steady_clock::now();
   {
     py::gil_scoped_release rel;
@@ -666,6 +669,7 @@ static py::dict read_unit_raw_py(const std::vector<std::string>& paths,
   d["zstd_jobs"] = zjobs;
   d["huf_jobs"] = hjobs;
   d["lz4_jobs"] = ljobs;
+  d["gzip_jobs"] = gjobs;
   py::list frows;
   for (auto r : ud.file_rows) frows.append(r);
   d["file_rows"] = frows;
@@ -904,7 +908,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gpu_snappy") = false, py::arg("gpu_zstd") = false,
         py::arg("gpu_zstd_frac") = 1.0, py::arg("gpu_delta") = false,
         py::arg("gpu_huf") = false, py::arg("gpu_lz4") = false,
-        py::arg("gpu_strings") = false);
+        py::arg("gpu_strings") = false, py::arg("gpu_gzip") = false);
   // the one descriptor column python looks at (fast-path eligibility)
   m.attr("UD_PRESENT") = (int)UD_PRESENT;
   // where a column's regions lie, and its GPU-decoded value encoding
@@ -1045,6 +1049,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)n ? (size_t)n : 1]);
     if (!lslz4::lz4_hadoop_decode(out.get(), n, (const uint8_t*)b.data(),
                                   (int64_t)b.size()))
+      return py::none();
+    return py::bytes((const char*)out.get(), (size_t)n);
+  });
+  // DEFLATE (inflate.h): a parquet GZIP page (gzip members or a zlib
+  // stream) and a bare DEFLATE stream; None for input they refuse
+  m.def("inflate_ref", [](py::bytes src, int64_t n) -> py::object {
+    std::string b = src;
+    if (n < 0) throw std::runtime_error("inflate_ref: n < 0");
+    std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)n ? (size_t)n : 1]);
+    if (!lsinfl::inflate_page(out.get(), n, (const uint8_t*)b.data(),
+                              (int64_t)b.size()))
+      return py::none();
+    return py::bytes((const char*)out.get(), (size_t)n);
+  });
+  m.def("inflate_raw_ref", [](py::bytes src, int64_t n) -> py::object {
+    std::string b = src;
+    if (n < 0) throw std::runtime_error("inflate_raw_ref: n < 0");
+    std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)n ? (size_t)n : 1]);
+    if (!lsinfl::inflate_raw(out.get(), n, (const uint8_t*)b.data(),
+                             (int64_t)b.size()))
       return py::none();
     return py::bytes((const char*)out.get(), (size_t)n);
   });

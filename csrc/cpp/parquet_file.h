@@ -770,6 +770,9 @@ class ParquetFile {
     // gpu_lz4 mode: the LZ4_RAW pages of a host_deferred chunk, by file
     // offset: the GPU decodes them (csrc/hip/lz4.hip)
     std::vector<DeferPage> lz4_pages;
+    // gpu_gzip mode: the GZIP pages of a host_deferred chunk, by file
+    // offset: the GPU decodes them (csrc/hip/gzip.hip)
+    std::vector<DeferPage> gzip_pages;
     // LIST columns: rows -> element ranges (+1 sentinel) and per-row
     // validity; values/validity above then describe the ELEMENTS
     bool is_list = false;
@@ -834,28 +837,30 @@ class ParquetFile {
   // gpu_lz4: LZ4_RAW pages under the snappy route's conditions go to
   // lz4_pages by file offset (csrc/hip/lz4.hip decodes them); the chunk is
   // host_deferred with no payload, so its descriptor is cached.
+  // gpu_gzip: the same for GZIP pages, to gzip_pages (csrc/hip/gzip.hip).
+  // Without it they are deferred to the host pool like zstd pages.
   ChunkData read_chunk(size_t rg, size_t col, bool gpu_snappy = false,
                        bool defer_host = false, bool gpu_zstd = false,
                        bool gpu_delta = false, bool gpu_huf = false,
-                       bool gpu_lz4 = false) const {
+                       bool gpu_lz4 = false, bool gpu_gzip = false) const {
     gpu_huf = gpu_huf && (defer_host || gpu_zstd);
     // descriptor cache: lakehouse files are immutable, and deferred /
     // gpu-staged chunks are pure page descriptors (no payload) — cache
     // them so repeated scans skip the per-page thrift header walk
     // (reference analog: the global metadata cache, session.rs:86-105)
-    // (five flag bits below the column index)
-    uint64_t ckey = ((uint64_t)rg << 25) | ((uint64_t)col << 5) |
+    // (six flag bits below the column index)
+    uint64_t ckey = ((uint64_t)rg << 26) | ((uint64_t)col << 6) |
                     (defer_host ? 1u : 0u) | (gpu_snappy ? 2u : 0u) |
                     (gpu_zstd ? 4u : 0u) | (gpu_huf ? 8u : 0u) |
-                    (gpu_lz4 ? 16u : 0u);
-    if (defer_host || gpu_snappy || gpu_zstd || gpu_lz4) {
+                    (gpu_lz4 ? 16u : 0u) | (gpu_gzip ? 32u : 0u);
+    if (defer_host || gpu_snappy || gpu_zstd || gpu_lz4 || gpu_gzip) {
       std::lock_guard<std::mutex> lk(chunk_mu_);
       auto it = chunk_meta_cache_.find(ckey);
       if (it != chunk_meta_cache_.end()) return *it->second;
     }
     ChunkData out_cached = read_chunk_impl(rg, col, gpu_snappy, defer_host,
                                            gpu_zstd, gpu_delta, gpu_huf,
-                                           gpu_lz4);
+                                           gpu_lz4, gpu_gzip);
     if ((out_cached.host_deferred || out_cached.gpu_compressed) &&
         out_cached.values.empty() && out_cached.validity.empty() &&
         out_cached.dict.empty() && out_cached.comp.empty()) {
@@ -871,7 +876,8 @@ class ParquetFile {
                             bool gpu_zstd = false,
                             bool gpu_delta = false,
                             bool gpu_huf = false,
-                            bool gpu_lz4 = false) const {
+                            bool gpu_lz4 = false,
+                            bool gpu_gzip = false) const {
     const RowGroup& g = meta_.row_groups.at(rg);
     const ColumnMeta& cm = g.columns.at(col);
     const ColumnDesc& cd = cols_.at(col);
@@ -957,8 +963,9 @@ class ParquetFile {
         values_seen += ph.num_values;
         continue;
       }
-      if (gpu_lz4 && cm.codec == CODEC_LZ4_RAW && ph.type == PAGE_DATA &&
-          ph.encoding == ENC_PLAIN && !cd.nullable &&
+      if (((gpu_lz4 && cm.codec == CODEC_LZ4_RAW) ||
+           (gpu_gzip && cm.codec == CODEC_GZIP)) &&
+          ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN && !cd.nullable &&
           cd.physical != PT_BOOLEAN && cd.physical != PT_BYTE_ARRAY &&
           cd.physical != PT_FLBA && cd.physical != PT_INT96 && !cd.is_list &&
           out.dict.empty() && out.values.empty()) {
@@ -972,7 +979,7 @@ class ParquetFile {
         dp.out_off = out.values_len;
         dp.out_len = ph.uncompressed_size;
         dp.codec = cm.codec;
-        out.lz4_pages.push_back(dp);
+        (cm.codec == CODEC_GZIP ? out.gzip_pages : out.lz4_pages).push_back(dp);
         out.values_len += ph.uncompressed_size;
         values_seen += ph.num_values;
         continue;
@@ -999,7 +1006,7 @@ class ParquetFile {
       }
       if (defer_host &&
           (cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED ||
-           cm.codec == CODEC_LZ4_RAW) &&
+           cm.codec == CODEC_LZ4_RAW || cm.codec == CODEC_GZIP) &&
           ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN && !cd.nullable &&
           cd.physical != PT_BOOLEAN && cd.physical != PT_BYTE_ARRAY &&
           cd.physical != PT_FLBA && cd.physical != PT_INT96 && !cd.is_list &&
@@ -1020,7 +1027,7 @@ class ParquetFile {
       }
       if (out.host_deferred &&
           !((cm.codec == CODEC_ZSTD || cm.codec == CODEC_UNCOMPRESSED ||
-             cm.codec == CODEC_LZ4_RAW) &&
+             cm.codec == CODEC_LZ4_RAW || cm.codec == CODEC_GZIP) &&
             ph.type == PAGE_DATA && ph.encoding == ENC_PLAIN)) {
         return read_chunk_impl(rg, col, false, false);  // mixed: redo staged
       }

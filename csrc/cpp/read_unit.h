@@ -190,6 +190,10 @@ struct UnitStage {
   // huf_src (the two share the tail of comp)
   std::vector<int64_t> lz4_jobs;
   std::vector<HostJob> lz4_src;
+  // GZIP pages, decoded by gzip.hip: as lz4_jobs and lz4_src (all three
+  // share the tail of comp)
+  std::vector<int64_t> gzip_jobs;
+  std::vector<HostJob> gzip_src;
   std::vector<std::unique_ptr<StrDecoded>> str_cols;
   int64_t values_size = 0, validity_size = 0, dicts_size = 0, soffs_size = 0,
           comp_size = 0;
@@ -199,7 +203,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     const std::vector<std::string>& paths, const std::vector<std::string>& names,
     bool gpu_snappy = false, bool gpu_zstd = false,
     double gpu_zstd_frac = 1.0, bool gpu_delta = false, bool gpu_huf = false,
-    bool gpu_lz4 = false, bool gpu_strings = false) {
+    bool gpu_lz4 = false, bool gpu_strings = false, bool gpu_gzip = false) {
   auto st = std::make_unique<UnitStage>();
   UnitStage& S = *st;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -249,7 +253,7 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
             gpu_zstd && ((double)((i * 2654435761u) % 1000) < gpu_zstd_frac * 1000.0);
         fd.chunks[t.c][t.rg] =
             fd.f->read_chunk(t.rg, fd.col_idx[t.c], gpu_snappy, true, this_gpu_zstd,
-                             gpu_delta, gpu_huf, gpu_lz4);
+                             gpu_delta, gpu_huf, gpu_lz4, gpu_gzip);
       } catch (std::exception& e) {
         std::lock_guard<std::mutex> lk(err_mu);
         err = e.what();
@@ -304,7 +308,8 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
   // layout
   S.str_cols.resize(nfiles * names.size());
   int64_t vpos = 0, vapos = 0, dpos = 0, spos = 0;
-  int64_t huf_comp = 0;  // bytes of Huffman-only frames and LZ4 blocks so far
+  int64_t huf_comp = 0;  // bytes of Huffman-only frames, LZ4 blocks and GZIP
+                         // pages so far
   for (size_t fi = 0; fi < nfiles; fi++) {
     auto& fd = S.files[fi];
     for (size_t c = 0; c < names.size(); c++) {
@@ -544,6 +549,14 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
                 {(int)fi, lp.file_off, lp.comp_len, huf_comp, lp.out_len, lp.codec});
             huf_comp += lp.comp_len;
           }
+          for (auto& gp : ch.gzip_pages) {
+            S.gzip_jobs.insert(S.gzip_jobs.end(),
+                               {huf_comp, gp.comp_len, vpos + plen + gp.out_off,
+                                gp.out_len});
+            S.gzip_src.push_back(
+                {(int)fi, gp.file_off, gp.comp_len, huf_comp, gp.out_len, gp.codec});
+            huf_comp += gp.comp_len;
+          }
           if (ch.gpu_compressed) {
             for (auto& cp : ch.comp_pages) {
               auto& jobs = (cp.codec == CODEC_ZSTD) ? S.zstd_jobs : S.snappy_jobs;
@@ -640,8 +653,8 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
     }
   }
 
-  // the Huffman-only frames and the LZ4 blocks go behind the chunk-owned
-  // page bodies in comp
+  // the Huffman-only frames, the LZ4 blocks and the GZIP pages go behind
+  // the chunk-owned page bodies in comp
   for (size_t i = 0; i < S.huf_src.size(); i++) {
     S.huf_jobs[4 * i] += S.comp_size;
     S.huf_src[i].dst_off += S.comp_size;
@@ -649,6 +662,10 @@ inline std::unique_ptr<UnitStage> read_unit_stage1(
   for (size_t i = 0; i < S.lz4_src.size(); i++) {
     S.lz4_jobs[4 * i] += S.comp_size;
     S.lz4_src[i].dst_off += S.comp_size;
+  }
+  for (size_t i = 0; i < S.gzip_src.size(); i++) {
+    S.gzip_jobs[4 * i] += S.comp_size;
+    S.gzip_src[i].dst_off += S.comp_size;
   }
   S.comp_size += huf_comp;
 
@@ -750,16 +767,18 @@ inline void read_unit_fill(UnitStage& S, uint8_t* values, uint8_t* validity,
   // deferred pages: decompress straight from the file mmap into the
   // destination buffer (one pass, zero staging)
   // and, in the same sweep of the pool, the frames of the Huffman-only
-  // pages and the LZ4 blocks from the mmap into comp for the GPU (tens of
-  // MB per unit: not for the serial copy above)
+  // pages, the LZ4 blocks and the GZIP pages from the mmap into comp for
+  // the GPU (tens of MB per unit: not for the serial copy above)
   const int64_t nhost = (int64_t)S.host_jobs.size();
   const int64_t nhuf = comp ? (int64_t)S.huf_src.size() : 0;
   const int64_t nlz4 = comp ? (int64_t)S.lz4_src.size() : 0;
-  ThreadPool::instance().parallel_for(nhost + nhuf + nlz4, [&](int64_t i) {
+  const int64_t ngzip = comp ? (int64_t)S.gzip_src.size() : 0;
+  ThreadPool::instance().parallel_for(nhost + nhuf + nlz4 + ngzip, [&](int64_t i) {
     if (i >= nhost) {
-      const UnitStage::HostJob& hs = i - nhost < nhuf
-                                         ? S.huf_src[i - nhost]
-                                         : S.lz4_src[i - nhost - nhuf];
+      const UnitStage::HostJob& hs =
+          i - nhost < nhuf          ? S.huf_src[i - nhost]
+          : i - nhost - nhuf < nlz4 ? S.lz4_src[i - nhost - nhuf]
+                                    : S.gzip_src[i - nhost - nhuf - nlz4];
       std::memcpy(comp + hs.dst_off,
                   S.files[hs.file_idx].f->data_at(hs.file_off),
                   (size_t)hs.comp_len);

@@ -1229,6 +1229,33 @@ static std::vector<torch::Tensor> lz4_decompress(torch::Tensor src,
   return {dst, lz4_decompress_into(src, jobs, dst)};
 }
 
+// GPU GZIP (gzip.hip): GZIP pages (gzip members or a zlib stream), one wave
+// per page, no scratch. jobs as for snappy. gzip_decompress_into writes
+// into an existing device buffer; gzip_decompress allocates total_dst bytes
+// and returns (dst, status) for direct tests. status[i] != 0: page i is not
+// a valid page (part of its own output range may be written). CRC32 and
+// Adler-32 are not checked on this route.
+static torch::Tensor gzip_decompress_into(torch::Tensor src, torch::Tensor jobs,
+                                          torch::Tensor dst) {
+  CHECK_GPU(src);
+  CHECK_GPU(jobs);
+  CHECK_GPU(dst);
+  TORCH_CHECK(jobs.dim() == 2 && jobs.size(1) == 4 && jobs.is_contiguous(),
+              "jobs must be a contiguous [m][4] table");
+  auto status = torch::empty({jobs.size(0)}, src.options().dtype(torch::kInt32));
+  launch_gzip_decompress(src.data_ptr<uint8_t>(), jobs.data_ptr<int64_t>(),
+                         jobs.size(0), dst.data_ptr<uint8_t>(),
+                         status.data_ptr<int32_t>(), cur_stream());
+  return status;
+}
+
+static std::vector<torch::Tensor> gzip_decompress(torch::Tensor src,
+                                                  torch::Tensor jobs,
+                                                  int64_t total_dst) {
+  auto dst = torch::empty({total_dst}, src.options());
+  return {dst, gzip_decompress_into(src, jobs, dst)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ann_scores", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, false); });
   m.def("ann_scores_t", [](torch::Tensor X, torch::Tensor Q) { return ann_scores(X, Q, true); });
@@ -1342,6 +1369,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("snappy_decompress_into", &snappy_decompress_into);
   m.def("lz4_decompress", &lz4_decompress);
   m.def("lz4_decompress_into", &lz4_decompress_into);
+  m.def("gzip_decompress", &gzip_decompress);
+  m.def("gzip_decompress_into", &gzip_decompress_into);
   m.def("scan_unit_uselast", &scan_unit_uselast, py::arg("vals"),
         py::arg("validity"), py::arg("dicts"), py::arg("runs"), py::arg("soffs"),
         py::arg("desc"), py::arg("nfiles"), py::arg("ncols"), py::arg("pk_ci"),

@@ -199,7 +199,7 @@ void launch_str_pred(const OffT* offsets, const uint8_t* bytes, int64_t nbytes,
                      int64_t op_nmeta, int wave_shape, uint8_t* out, int64_t n,
                      hipStream_t s);
 
-// snappy.hip, lz4.hip, zstd.hip, zstd_huf.hip
+// snappy.hip, lz4.hip, gzip.hip, zstd.hip, zstd_huf.hip
 void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
                               int64_t njobs, uint8_t* dst, int32_t* status,
                               hipStream_t s);
@@ -209,6 +209,13 @@ void launch_snappy_decompress(const uint8_t* src, const int64_t* jobs,
 void launch_lz4_decompress(const uint8_t* src, const int64_t* jobs,
                            int64_t njobs, uint8_t* dst, int32_t* status,
                            hipStream_t s);
+// GZIP pages (gzip members or a zlib stream); jobs as for snappy. Framing,
+// ISIZE and the output length are checked, CRC32 and Adler-32 are not. A
+// page that fails gets a non-zero status (it may be partly written, inside
+// its own output range)
+void launch_gzip_decompress(const uint8_t* src, const int64_t* jobs,
+                            int64_t njobs, uint8_t* dst, int32_t* status,
+                            hipStream_t s);
 void launch_zstd_decompress(const uint8_t* src, const int64_t* jobs,
                             int64_t njobs, uint8_t* dst, uint8_t* scratch,
                             int64_t nblocks, int32_t* status, hipStream_t s);

@@ -113,6 +113,16 @@ _GPU_HUF = _os.environ.get("LAKESOUL_GPU_HUF", "1") != "0"
 # pages). Measured: profiles/r04_gpu_lz4.md.
 _GPU_LZ4 = _os.environ.get("LAKESOUL_GPU_LZ4", "0") == "1"
 
+# GZIP pages of REQUIRED fixed-width PLAIN columns: the host pool inflates
+# them straight into the values buffer (csrc/cpp/inflate.h), as it does
+# zstd pages. LAKESOUL_GPU_GZIP=1 sends them to the GPU instead, one wave
+# per page (csrc/hip/gzip.hip); that route checks framing, ISIZE and the
+# output length but not CRC32. Off by default: on a pyarrow-written GZIP
+# copy of the headline table the GPU route scans in 575 ms against 217 ms
+# (a wave decodes a page's symbols one by one, and a scan unit holds only a
+# few hundred pages). Measured: profiles/r08_gpu_gzip.md.
+_GPU_GZIP = _os.environ.get("LAKESOUL_GPU_GZIP", "0") == "1"
+
 
 # String columns whose chunks are all PLAIN (or all dictionary-encoded):
 # ship the raw streams and let the GPU strip the prefixes / expand the
@@ -134,7 +144,7 @@ def fetch_raw(files: List[str], names: List[str]) -> dict:
     with timing.phase("host_fetch"):
         raw = cpp().read_unit_raw(files, names, 0, True, True, _GPU_ZSTD,
                                   _GPU_ZSTD_FRAC, _GPU_DELTA, _GPU_HUF,
-                                  _GPU_LZ4, _GPU_STRINGS)
+                                  _GPU_LZ4, _GPU_STRINGS, _GPU_GZIP)
     if timing.ENABLED:
         timing._acc["fetch.stage1"] += raw["t_stage1_us"] / 1e6
         timing._acc["fetch.s1_open"] += raw["t_open_us"] / 1e6
@@ -158,7 +168,7 @@ class UnitTransfer:
         # data — ship only the host-filled gaps (for all-zstd units the
         # H2D volume drops to the compressed bytes)
         jobs_host = []
-        for k in ("snappy_jobs", "zstd_jobs", "huf_jobs", "lz4_jobs"):
+        for k in ("snappy_jobs", "zstd_jobs", "huf_jobs", "lz4_jobs", "gzip_jobs"):
             t = raw.get(k)
             if t is not None and t.numel():
                 jobs_host.append(t.view(-1, 4))
@@ -212,6 +222,11 @@ class UnitTransfer:
         self.lz4_jobs = (
             raw["lz4_jobs"].view(-1, 4).to(device, non_blocking=True)
             if raw.get("lz4_jobs") is not None and raw["lz4_jobs"].numel()
+            else None
+        )
+        self.gzip_jobs = (
+            raw["gzip_jobs"].view(-1, 4).to(device, non_blocking=True)
+            if raw.get("gzip_jobs") is not None and raw["gzip_jobs"].numel()
             else None
         )
 
@@ -281,6 +296,11 @@ def read_unit_gpu(scan, unit, raw: Optional[dict] = None) -> Optional[Batch]:
         status = hip().lz4_decompress_into(transfer.comp, transfer.lz4_jobs, vals)
         if bool((status != 0).any()):
             raise RuntimeError(f"GPU lz4 decompression failed: status={int((status != 0).sum())} pages")
+    if transfer.gzip_jobs is not None:
+        # GPU GZIP: GZIP pages straight into the values buffer
+        status = hip().gzip_decompress_into(transfer.comp, transfer.gzip_jobs, vals)
+        if bool((status != 0).any()):
+            raise RuntimeError(f"GPU gzip decompression failed: status={int((status != 0).sum())} pages")
     if transfer.zstd_jobs is not None:
         # GPU zstd: the from-scratch RFC 8878 decoder (csrc/hip/zstd.hip)
         # decompresses zstd page frames straight into the values buffer —

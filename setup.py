@@ -46,6 +46,7 @@ if _WITH_HIP:
                 os.path.join("csrc", "hip", "fastscan.hip"),
                 os.path.join("csrc", "hip", "snappy.hip"),
                 os.path.join("csrc", "hip", "lz4.hip"),
+                os.path.join("csrc", "hip", "gzip.hip"),
                 os.path.join("csrc", "hip", "zstd.hip"),
                 os.path.join("csrc", "hip", "zstd_huf.hip"),
                 os.path.join("csrc", "hip", "delta.hip"),
